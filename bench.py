@@ -13,11 +13,19 @@ broadcast of the packed weights from rank 0.
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks (fresh child
 processes, before anything touches a GPU) - the same layout torch.distributed.run would give.
 
-Extra legs on rank 0:
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  `--dump-outputs DIR` then
+also writes what the timed path returned in its last step - the denoised latents [1, F, 4, h, w] of the clip - as
+DIR/latents.npy (float32; rank r > 0 of an N-GPU run writes DIR/latents_rank<r>.npy).  Weights and inputs are seeded, so
+the same arguments give the same inputs in every run and two builds can be compared output for output.
+
+Extra legs on rank 0, only with --full (--no-cpu-baseline / --no-decode / --no-profile drop one of them; --end-to-end,
+--train-step and --clips-per-gpu K add their own):
   roofline      the dominant kernel family - the implicit-GEMM convolutions / linear layers (igemm*_kernel) and the two fused forms that
                 took launches over from it (ffn320_kernel: GEGLU feed-forward, lnlin320_kernel: LayerNorm + Q|K|V projection):
                 algorithmic flops / hipEvent time of every launch of one extra clip, against the 2.5 PFLOP/s dense fp16 MFMA peak.
-                Also reported: the spatial attention kernel and the whole path (executed flops / clip wall time).
+                Also reported: the spatial attention kernel and the whole path (executed flops / clip wall time), and the socket
+                power sampled over the timed steps.
+  decode        the VAE decode of the loop's output (decode_chunk_size 8 + tensor2vid), beside the headline, never in it.
   cpu_baseline  the CPU oracle (oracle/, fp32 PyTorch on the host cores): ONE real loop iteration of the full-width U-Net +
                 ControlNet at the benched geometry itself (14 x 576 x 1024: latent 72 x 128, ~123 TFLOP of fp32, ~200 s on 15 threads)
                 after a 64 x 64 px warm-up; reference-executed flops are counted exactly with meta tensors.  It runs in a child process
@@ -67,6 +75,8 @@ def traffic_per_launch(args):
             "source": os.path.relpath(best, os.path.dirname(os.path.abspath(__file__)))}
 
 
+T_START = time.time()
+DUMP_LIMIT_BYTES = 64 << 20              # --dump-outputs: at most this much in all (a seeded sample of anything larger)
 PEAK_FP16_DENSE_TFLOPS = 2500.0          # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 SVD = dict(block_out_channels=(320, 640, 1280, 1280), num_attention_heads=(5, 10, 20, 20), cross_attention_dim=1024,
            addition_time_embed_dim=256, projection_class_embeddings_input_dim=768, layers_per_block=2, num_frames=14)
@@ -350,6 +360,18 @@ def broadcast_packed(tensors, src=0, bucket_bytes=1 << 30):
     return gb, time.perf_counter() - t0, n_coll
 
 
+def dump_outputs(directory, latents, rank, world):
+    """--dump-outputs: the denoised latents the timed path returned in its last step, as float32 .npy.  Each rank keeps
+    to its share of DUMP_LIMIT_BYTES; a larger array is replaced by a fixed seeded sample of its flattened elements."""
+    os.makedirs(directory, exist_ok=True)
+    a = latents.detach().to(torch.float32).cpu().numpy()
+    limit = DUMP_LIMIT_BYTES // world // a.itemsize
+    if a.size > limit:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=limit, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(directory, "latents.npy" if rank == 0 else f"latents_rank{rank}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -358,6 +380,10 @@ def main():
     ap.add_argument("--workload", default="L", choices=list(WORKLOADS))
     ap.add_argument("--infer-steps", type=int, default=25)
     ap.add_argument("--frames", type=int, default=14)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (roofline + socket power, VAE decode, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's denoised latents as DIR/latents.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--camera", action="store_true",
@@ -380,6 +406,10 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="(test hook) start the ranks, rendezvous over gloo on the CPU, shard the clips, print the layout and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.end_to_end or args.train_step or args.clips_per_gpu > 1):
+        ap.error("--end-to-end, --train-step and --clips-per-gpu are legs of a --full run")
 
     if args.cpu_baseline_child:                    # CPU-only child of the cpu_baseline leg: never touches the GPU
         height, width = args.child_hw
@@ -467,27 +497,31 @@ def main():
     for _ in range(args.warmup):
         out = run_clip()
     fence()
-    power = PowerSampler(dev.index or 0).start() if (rank == 0 and world == 1) else None
+    power = PowerSampler(dev.index or 0).start() if (args.full and rank == 0 and world == 1) else None
     t0 = time.perf_counter()
     for k in range(args.steps):
         out = run_clip()
     fence()
     elapsed = time.perf_counter() - t0
     power_w = power.result() if power is not None else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     # the CPU leg starts only now: beside the timed clips its host threads and the launch thread perturbed each other (and the
     # power sampler).  It overlaps the roofline clip below, whose numbers are hipEvent brackets on the device.
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # one REAL iteration of the benched workload itself (72 x 128: ~123 TFLOP of fp32, ~200 s on 15 threads, inside
-        # the child's budget; rounds 1-4 timed 40 x 72 and scaled by flops)
+        # the child's budget; rounds 1-4 timed 40 x 72 and scaled by flops).  The budget ends 9 minutes after start-up at the
+        # latest, so that a --full run exits within 10 minutes
         sample_latent = (height // 8, width // 8)
-        cpu_child = CpuBaselineChild(args.frames, height, width, args.infer_steps, sample_latent)
+        cpu_child = CpuBaselineChild(args.frames, height, width, args.infer_steps, sample_latent,
+                                     budget_s=round(min(600.0, max(60.0, 540.0 - (time.time() - T_START)))))
     # roofline leg: one more clip, outside the timed region, launched eagerly (a graph replay bypasses the C-ABI entry
     # points, so their hipEvent brackets would see nothing) with events around every igemm / attention launch on the
     # launch stream.  Same kernels, same shapes, same order as the timed clips.
     # decode leg (beside the headline, never in it): the step right after the loop - decode_latents at the
     # reference script's decode_chunk_size = 8 + tensor2vid - on a random-init AutoencoderKLTemporalDecoder at the SVD widths
     extra = {}
-    if rank == 0 and not args.no_decode:
+    if args.full and rank == 0 and not args.no_decode:
         from posetraj_amd import AutoencoderKLTemporalDecoder
         from posetraj_amd.pipeline_stable_video_diffusion_controlnet import tensor2vid
         vae = AutoencoderKLTemporalDecoder(**SVD_VAE).init_random_(seed=300, device=dev)
@@ -570,7 +604,7 @@ def main():
         del pipeK, latK, ilK, embK, condK, outK
         torch.cuda.empty_cache()
     prof = {}
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         with ops.Profiler():
             tc0 = time.perf_counter()
             run_clip(use_graph=False)

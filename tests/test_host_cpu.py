@@ -224,6 +224,24 @@ def test_bench_power_sampler_is_never_fatal(tmp_path):
     assert r["median"] == 1290 and r["cap"] == 1400 and r["card"].startswith("highest")
 
 
+def test_bench_dump_outputs_writes_float32_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the latents as float32 .npy, whole when they fit; above the budget a seeded sample that
+    is the same in every run."""
+    import numpy as np
+    import torch
+    import bench
+    x = torch.randn(1, 14, 4, 8, 8, generator=torch.Generator().manual_seed(0)).to(torch.float16)
+    bench.dump_outputs(str(tmp_path / "a"), x, 0, 1)
+    a = np.load(tmp_path / "a" / "latents.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), x, 1, 2)
+    b, c = np.load(tmp_path / "b" / "latents_rank1.npy"), np.load(tmp_path / "c" / "latents_rank1.npy")
+    assert b.dtype == np.float32 and b.nbytes == 2048 and np.array_equal(b, c)
+    assert np.isin(b, x.float().numpy().reshape(-1)).all()
+
+
 def test_non_cfg_branch_fails_like_the_reference(golden):
     """max_guidance_scale <= 1 (pipeline...:438,532): the reference doubles the control maps and added_time_ids
     unconditionally (:501-503, :521) and its ControlNet raises in add_embedding; the oracle's loop reaches the same error

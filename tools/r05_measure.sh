@@ -10,10 +10,10 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "${ONLY_PMC:-0}" = "0" ]; then
-python bench.py > $OUT/bench_L_default.json 2> $OUT/bench_L_default.err                      # exactly the driver's command (CPU baseline: one real 72 x 128 iteration)
-python bench.py --end-to-end --clips-per-gpu 2 --no-cpu-baseline > $OUT/bench_L_legs.json 2> $OUT/bench_L_legs.err
-python bench.py --train-step --no-cpu-baseline --no-decode --no-profile > $OUT/bench_L_train_step.json 2> $OUT/bench_L_train_step.err   # (no CPU leg beside the training child: its 15 host threads doubled the step's enqueue time)
-python bench.py --workload M --no-cpu-baseline > $OUT/bench_M.json 2> $OUT/bench_M.err
+python bench.py --full > $OUT/bench_L_default.json 2> $OUT/bench_L_default.err               # every default leg (CPU baseline: one real 72 x 128 iteration)
+python bench.py --full --end-to-end --clips-per-gpu 2 --no-cpu-baseline > $OUT/bench_L_legs.json 2> $OUT/bench_L_legs.err
+python bench.py --full --train-step --no-cpu-baseline --no-decode --no-profile > $OUT/bench_L_train_step.json 2> $OUT/bench_L_train_step.err   # (no CPU leg beside the training child: its 15 host threads doubled the step's enqueue time)
+python bench.py --full --workload M --no-cpu-baseline > $OUT/bench_M.json 2> $OUT/bench_M.err
 fi
 cd /tmp
 [ "${ONLY_PMC:-0}" = "0" ] && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_loop -o p -- python3 $REPO/bench.py --infer-steps 2 --steps 1 --warmup 1 --no-graph --no-profile --no-cpu-baseline --no-decode > $OUT/prof_loop.log 2>&1

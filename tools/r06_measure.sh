@@ -43,15 +43,15 @@ busy() {      # $1 = workload
 # files are committed from gpurun_out/<tag>/ afterwards
 if has L; then traffic L; mkdir -p profiles/r06/traffic; cp $OUT/summary_L_$TAG.json profiles/r06/traffic/; fi
 if has M; then traffic M; mkdir -p profiles/r06/traffic; cp $OUT/summary_M_$TAG.json profiles/r06/traffic/; fi
-if has base; then python bench.py $cpuflag > $OUT/bench_L_default.json 2> $OUT/bench_L_default.err; fi
-if has cam; then python bench.py --camera --no-cpu-baseline > $OUT/bench_L_camera.json 2> $OUT/bench_L_camera.err; fi
+if has base; then python bench.py --full $cpuflag > $OUT/bench_L_default.json 2> $OUT/bench_L_default.err; fi
+if has cam; then python bench.py --full --camera --no-cpu-baseline > $OUT/bench_L_camera.json 2> $OUT/bench_L_camera.err; fi
 if has legs; then
-  python bench.py --end-to-end --clips-per-gpu 2 --no-cpu-baseline > $OUT/bench_L_legs.json 2> $OUT/bench_L_legs.err
-  python bench.py --train-step --no-cpu-baseline --no-decode --no-profile > $OUT/bench_L_train_step.json 2> $OUT/bench_L_train_step.err
+  python bench.py --full --end-to-end --clips-per-gpu 2 --no-cpu-baseline > $OUT/bench_L_legs.json 2> $OUT/bench_L_legs.err
+  python bench.py --full --train-step --no-cpu-baseline --no-decode --no-profile > $OUT/bench_L_train_step.json 2> $OUT/bench_L_train_step.err
 fi
 if has M; then
-  python bench.py --workload M --no-cpu-baseline > $OUT/bench_M.json 2> $OUT/bench_M.err
-  python bench.py --workload M --no-cpu-baseline --clips-per-gpu 2 --no-decode > $OUT/bench_M_2clips.json 2> $OUT/bench_M_2clips.err
+  python bench.py --full --workload M --no-cpu-baseline > $OUT/bench_M.json 2> $OUT/bench_M.err
+  python bench.py --full --workload M --no-cpu-baseline --clips-per-gpu 2 --no-decode > $OUT/bench_M_2clips.json 2> $OUT/bench_M_2clips.err
   python tools/shape_report.py --workload M > $OUT/igemm_shapes_M_$TAG.txt 2>&1
   stats M
   python tools/energy_table.py --workload M > $OUT/energy_table_M_$TAG.txt 2>&1
