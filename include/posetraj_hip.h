@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 8
+#define PT_ABI_VERSION 9
 
 int         pt_abi_version(void);
 const char* pt_last_error(void);
@@ -99,6 +99,13 @@ int64_t pt_igemm_splitk_ws_bytes(const pt_igemm_params* p);
 /* test / tuning hook: force the tile configuration (0 = 256x256, 1 = 128x320 (no GEGLU), 2 = 128x128,
  * 3 = 256x320 (channel-aligned layers only; others fall back), 4 = 128x160, 5 = 256x32 (N <= 32: the condition encoder), -1 = automatic) */
 int pt_igemm_force_config(int32_t cfg);
+/* tuning hook (like pt_igemm_force_config): M tiles per rasterisation group (0 = automatic) and ablation bits of the
+ * kernels' tail (1 no global stores, 2 no epilogue, 4 no GELU on the GEGLU gate; results are wrong unless 0).  0, 0 = the product. */
+int pt_igemm_set_tuning(int32_t group_m, int32_t ablation);
+/* the launch plan pt_igemm_f16 would use for *p under the current hooks: tile configuration (numbered as in
+ * pt_igemm_force_config), split-K count (1 = none; > 1 only if p offers the workspace) and M tiles per rasterisation group.
+ * Host only: validates p like pt_igemm_f16, dereferences none of its pointers and touches no device. */
+int pt_igemm_plan(const pt_igemm_params* p, int32_t* cfg, int32_t* splits, int32_t* group_m);
 /* tuning hook: device buffer of `capacity` uint64 that the next launches of the 256x256 / 256x320 kernels fill with
  * s_memtime stamps, 16 slots per wave ((workgroup * 8 + wave) * 16 + {0: start, 1: first K tile landed, 2: main loop
  * done, 3: stores issued, 4: epilogue barrier passed, 5 + 2c / 6 + 2c: epilogue chunk c staged in LDS / finished});

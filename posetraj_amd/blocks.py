@@ -19,7 +19,6 @@ batch-interleaved context index of the temporal blocks (``modified_svd.py:152-15
 from __future__ import annotations
 
 import math
-import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -30,7 +29,7 @@ from .packing import pack_conv2d, pack_conv_t3, pack_linear, vec16
 
 HEAD_DIMS = (64, 128)
 # feed-forward intermediates larger than this are produced and consumed in row chunks (TransformerSpatioTemporalModel._feed_forward)
-FF_CHUNK_BYTES = int(os.environ.get("PT_FF_CHUNK_MB", "0")) << 20
+FF_CHUNK_BYTES = 0                 # (128 << 20: the M-slab form of DESIGN 8 (c), A/B)
 
 
 class RowStack:

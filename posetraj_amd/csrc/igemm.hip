@@ -768,7 +768,6 @@ using CfgN32 = Cfg<4, 1, 4, 2>;                // 256 x 32: 4 waves of 64 x 32 -
 // K tile + epilogue), with the per-configuration constants read off the s_memtime stamps / sweeps in
 // profiles/r01/igemm_stamps_v14.txt and igemm_cfg_sweep_v14.txt.  `fast` = channel-aligned K tiles (the pipelined
 // 256 x 256 and 256 x 320 kernels need it).
-double g_last_tile_cycles = 0.0, g_last_rounds = 0.0;       // of the configuration choose_cfg returned (model cycles per tile, rounds)
 int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast) {
     struct Opt { int bm, bn, slots; double pro, loop, epi, epi_geglu, epi_side; };
     static const Opt pipelined[5] = {
@@ -782,7 +781,7 @@ int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast) {
                                                              // costs 0.68 of the 10-phase kernel's per output, not 0.77 - 80640 x 320 x 2880 / 5760, the
                                                              // level-0 convolutions of the 320 x 576 workload, ran 13 / 20 % slower here than on 256 x 320)
     };   // round 6: with these constants and the split rule below the model picks the fastest measured configuration for 59 of the 60
-         // shapes of profiles/r06/igemm_cfg_sweep_{L,M}_r06c.txt (tools/cfg_model_check.py restates the model and scores it, CPU only)
+         // shapes of profiles/r06/igemm_cfg_sweep_{L,M}_r06c.txt (tools/cfg_model_check.py scores it through pt_igemm_plan, CPU only)
     int best = 2; double best_t = 1e300;
     for (int i = 0; i < 5; ++i) {
         if (i == 1 && act == 1) continue;                    // odd TN: no GEGLU pairs
@@ -797,7 +796,7 @@ int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast) {
         const int wave_w = o.bn / (i == 0 || i == 3 ? 2 : (i == 1 ? 4 : (i == 2 ? 2 : 1)));
         const double ragged = (N > wave_w && N % wave_w != 0) ? 1.3 : 1.0;
         const double t = rounds * tile * ragged;
-        if (t < best_t * 0.999) { best_t = t; best = i; g_last_tile_cycles = tile; g_last_rounds = tiles / o.slots; }
+        if (t < best_t * 0.999) { best_t = t; best = i; }
     }
     return best;
 }
@@ -816,18 +815,21 @@ int choose_group(int tiles_m, int tiles_n, double a_bytes, double w_bytes, int c
     return best;
 }
 
-template <class CF>
-void launch(const KParams& kp, bool fast, hipStream_t s) {
+template <class CF, bool FAST>
+void launch(const KParams& kp, hipStream_t s) {
     static bool attr_done[64] = {};                          // the opt-in is per device
     const int dev = pt_device();
     if (!attr_done[dev]) {
-        (void)hipFuncSetAttribute((const void*)igemm_kernel<CF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-        (void)hipFuncSetAttribute((const void*)igemm_kernel<CF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
+        (void)hipFuncSetAttribute((const void*)igemm_kernel<CF, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
         attr_done[dev] = true;
     }
-    const unsigned nblk = (unsigned)(kp.tiles_m * kp.tiles_n);
-    if (fast) hipLaunchKernelGGL((igemm_kernel<CF, true>), dim3(nblk), dim3(CF::NT), CF::SMEM, s, kp);
-    else      hipLaunchKernelGGL((igemm_kernel<CF, false>), dim3(nblk), dim3(CF::NT), CF::SMEM, s, kp);
+    hipLaunchKernelGGL((igemm_kernel<CF, FAST>), dim3((unsigned)(kp.tiles_m * kp.tiles_n)), dim3(CF::NT), CF::SMEM, s, kp);
+}
+
+template <class CF>
+void launch(const KParams& kp, bool fast, hipStream_t s) {
+    if (fast) launch<CF, true>(kp, s);
+    else      launch<CF, false>(kp, s);
 }
 
 typedef void (*pipe_kernel_t)(const KParams);
@@ -859,7 +861,10 @@ void launch10(const KParams& kp, hipStream_t s) {
     hipLaunchKernelGGL(table[var], dim3((unsigned)(kp.tiles_m * kp.tiles_n * kp.splits)), dim3(512), CfgT320::SMEM + TRASH, s, kp);
 }
 
-int g_force_cfg = -1;
+// Process-wide hooks (single-threaded setters, read by every later plan).
+int g_force_cfg = -1;     // pt_igemm_force_config
+int g_group_m = 0;        // pt_igemm_set_tuning: M tiles per rasterisation group (0 = choose_group)
+int g_ablation = 0;       // pt_igemm_set_tuning: KParams::dbg
 
 }  // namespace
 
@@ -878,14 +883,22 @@ extern "C" int pt_igemm_force_config(int32_t cfg) {
     return 0;
 }
 
+// tuning hook (tools/igemm_bench.py --group-m / --ablation): rasterisation group size (0 = automatic) and ablation bits of the
+// kernels' tail (KParams::dbg; results are WRONG unless 0)
+extern "C" int pt_igemm_set_tuning(int32_t group_m, int32_t ablation) {
+    PT_CHECK(group_m >= 0 && ablation >= 0, "pt_igemm_set_tuning: group_m=%d ablation=%d", group_m, ablation);
+    g_group_m = group_m;
+    g_ablation = ablation;
+    return 0;
+}
+
 // Split-K plan for small-M problems (level 3: 64 tiles of 256 x 320 on 256 CUs; 20 tiles at the 320 x 576 workload):
 // `splits` workgroups per output tile, each >= 6 K tiles, until the launch has about one workgroup per CU.  Only the
 // 256 x 320 kernel implements it (channel-aligned K, no GEGLU, 16-byte-aligned rows for the reducer).  Short reductions
 // (K < 3072) stay un-split: there the 128-row tiles already give one workgroup per CU and the two launches + fp32 slab round
 // trip of split-K lose to them (2520 x 1280 x 1280: 38.7 us split, 19.7 us on 128 x 128 tiles; tools/micro/igemm_cfg_sweep.py).
 static int plan_splits(const pt_igemm_params& p, bool fast, bool vec_ok) {
-    static const int off = getenv("PT_IGEMM_NO_SPLITK") ? atoi(getenv("PT_IGEMM_NO_SPLITK")) : 0;
-    if (off || !fast || !vec_ok || p.act == 1 || p.N % 8 != 0) return 1;
+    if (!fast || !vec_ok || p.act == 1 || p.N % 8 != 0) return 1;
     const int tiles = ((p.M + 255) / 256) * ((p.N + 319) / 320), nk = p.Kpad / BK;
     if (tiles > 128 || nk < 48) return 1;
     // round 6: where the 128 x 128 tiles alone give (nearly) one workgroup per slot - >= 300 tiles for the 512 slots - reductions up to
@@ -901,21 +914,18 @@ static int plan_splits(const pt_igemm_params& p, bool fast, bool vec_ok) {
     return s < 2 ? 1 : s;
 }
 
-extern "C" int64_t pt_igemm_splitk_ws_bytes(const pt_igemm_params* pp) {
-    const pt_igemm_params& p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.Kpad <= 0 || p.C0 <= 0) return 0;
-    const int Ctot = p.C0 + p.C1;
-    const bool fast = (Ctot % BK == 0) && (p.C0 % BK == 0) && (p.Kpad == p.K);
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    const bool vec_ok = !p.out_f32 && (p.N % 8 == 0) && (p.ldo % 8 == 0) && al16(p.out) && (!p.res || (p.ldr % 8 == 0 && al16(p.res))) && al16(p.res_lo) && al16(p.out_lo) &&
-                        (!p.vec || (p.ldv % 8 == 0 && al16(p.vec))) && (!p.blend || (p.ldb % 8 == 0 && al16(p.blend)));
-    if (g_force_cfg >= 0 && g_force_cfg != 3) return 0;
-    const int s = plan_splits(p, fast, vec_ok);
-    return s > 1 ? (int64_t)s * p.M * p.N * 4 : 0;
-}
+namespace {
 
-extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
-    const pt_igemm_params& p = *pp;
+// Everything pt_igemm_f16 decides before it launches: the parameter checks, the tile configuration, the split-K count
+// (`ws_bytes` of workspace wanted, `splits` > 1 only if the caller offered that much) and the rasterisation group.  Host only:
+// touches no device, so pt_igemm_splitk_ws_bytes and pt_igemm_plan ask it too.
+struct Plan {
+    bool fast, foldx, vec_ok;
+    int cfg, splits, gm, tiles_m, tiles_n;
+    int64_t ws_bytes;
+};
+
+int plan(const pt_igemm_params& p, Plan& pl) {
     const int Ctot = p.C0 + p.C1;
     PT_CHECK(p.x0 && p.w && p.out, "pt_igemm_f16: null pointer");
     PT_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "pt_igemm_f16: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
@@ -928,13 +938,63 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
     PT_CHECK(p.stride == 1 || p.stride == 2, "pt_igemm_f16: stride %d", p.stride);
     // the kernel packs each output pixel's top-left tap as two signed 16-bit coordinates; one-column kernels need no x
     // coordinate at all (foldx) and may be as wide as the 31-bit pixel index allows
-    const bool foldx = p.KW == 1 && p.pad_w == 0 && p.stride == 1 && !p.upsample2x && p.Wout == p.Win;
-    PT_CHECK((long long)p.Hout * p.stride + p.KH < 32000 && (foldx || (long long)p.Wout * p.stride + p.KW < 32000),
+    pl.foldx = p.KW == 1 && p.pad_w == 0 && p.stride == 1 && !p.upsample2x && p.Wout == p.Win;
+    PT_CHECK((long long)p.Hout * p.stride + p.KH < 32000 && (pl.foldx || (long long)p.Wout * p.stride + p.KW < 32000),
              "pt_igemm_f16: output extent %d x %d too large (a linear layer is Nimg = M, H = W = 1)", p.Hout, p.Wout);
     PT_CHECK((long long)p.Nimg * p.Hin * p.Win < (1ll << 31), "pt_igemm_f16: more than 2^31 input pixels");
     PT_CHECK(!(p.upsample2x && p.stride != 1), "pt_igemm_f16: upsample2x needs stride 1");
     PT_CHECK(p.act == 0 || p.act == 2 || (p.act == 1 && p.N % 32 == 0), "pt_igemm_f16: act must be 0, 1 (GEGLU, N %% 32 == 0) or 2 (SiLU)");
     PT_CHECK(p.vec_mode == 0 || p.vec, "pt_igemm_f16: vec_mode without vec");
+    PT_CHECK(!(p.res_post && !p.res), "pt_igemm_f16: res_post without res");
+    PT_CHECK(!(p.res_lo && !p.res), "pt_igemm_f16: res_lo without res");
+    PT_CHECK(!(p.out_lo && (p.out_f32 || p.act == 1)), "pt_igemm_f16: out_lo needs an fp16, non-GEGLU output");
+    PT_CHECK(p.cs_cols >= 0 && p.cs_cols % 8 == 0, "pt_igemm_f16: cs_cols=%d must be a non-negative multiple of 8", p.cs_cols);
+    const int nout = p.act == 1 ? p.N / 2 : p.N;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    pl.vec_ok = !p.out_f32 && (nout % 8 == 0) && (p.ldo % 8 == 0) && al16(p.out) && (!p.res || (p.ldr % 8 == 0 && al16(p.res))) && al16(p.res_lo) && al16(p.out_lo) &&
+                (!p.vec || (p.ldv % 8 == 0 && al16(p.vec))) && (!p.blend || (p.ldb % 8 == 0 && al16(p.blend)));
+    pl.fast = (Ctot % BK == 0) && (p.C0 % BK == 0) && (p.Kpad == p.K);
+    const int force = g_force_cfg;
+    int cfg = force >= 0 ? force : choose_cfg(p.M, p.N, p.Kpad / BK, p.act, p.res || p.blend, pl.fast);
+    const int want = (force < 0 || force == 3) ? plan_splits(p, pl.fast, pl.vec_ok) : 1;
+    pl.ws_bytes = want > 1 ? (int64_t)want * p.M * p.N * 4 : 0;
+    pl.splits = (want > 1 && p.splitk_ws && p.splitk_ws_bytes >= pl.ws_bytes) ? want : 1;   // else no workspace offered
+    if (pl.splits > 1) cfg = 3;
+    if (force < 0 && p.N <= 96 && p.act != 1 && pl.splits == 1) cfg = 5;   // tools/micro/igemm_n32_sweep.py: 2.6-4 x on N = 16 / 32, 1.5 x on 96
+    if (cfg == 3 && !pl.fast) cfg = p.act == 1 ? 0 : 1;     // the 256x320 kernel has no generic-K gather
+    PT_CHECK(!(cfg == 5 && p.act == 1), "pt_igemm_f16: the 256x32 configuration does not support GEGLU");
+    PT_CHECK(!(cfg == 1 && p.act == 1), "pt_igemm_f16: the 128x320 configuration does not support GEGLU");
+    pl.cfg = cfg;
+    const int bm = (cfg == 0 || cfg == 3 || cfg == 5) ? 256 : 128, bn = cfg == 0 ? 256 : (cfg == 2 ? 128 : (cfg == 4 ? 160 : (cfg == 5 ? 32 : 320)));
+    pl.tiles_m = (p.M + bm - 1) / bm;
+    pl.tiles_n = (p.N + bn - 1) / bn;
+    PT_CHECK((long long)pl.tiles_m * pl.tiles_n < (1ll << 31), "pt_igemm_f16: grid too large");
+    const double in_px = p.upsample2x ? p.M / 4.0 : (double)p.M * p.stride * p.stride;
+    pl.gm = g_group_m > 0 ? (g_group_m < pl.tiles_m ? g_group_m : pl.tiles_m)
+                          : choose_group(pl.tiles_m, pl.tiles_n, in_px * Ctot * 2.0, (double)p.N * p.K * 2.0, (cfg == 2 || cfg == 4) ? 64 : 32);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pt_igemm_plan(const pt_igemm_params* pp, int32_t* cfg, int32_t* splits, int32_t* group_m) {
+    Plan pl;
+    if (int rc = plan(*pp, pl)) return rc;
+    if (cfg) *cfg = pl.cfg;
+    if (splits) *splits = pl.splits;
+    if (group_m) *group_m = pl.gm;
+    return 0;
+}
+
+extern "C" int64_t pt_igemm_splitk_ws_bytes(const pt_igemm_params* pp) {
+    Plan pl;
+    return plan(*pp, pl) == 0 ? pl.ws_bytes : 0;
+}
+
+extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
+    const pt_igemm_params& p = *pp;
+    Plan pl;
+    if (int rc = plan(p, pl)) return rc;
     PT_CHECK(pt_zero_page(), "pt_igemm_f16: zero page not set (pt_set_zero_page)");
     KParams kp;
     kp.p = p;
@@ -942,61 +1002,33 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
     kp.zeros = (const f16*)pt_zero_page();
     kp.npad = (p.N + 127) / 128 * 128;
     kp.stamps = g_stamps; kp.stamps_cap = g_stamps_cap;
-    kp.foldx = foldx ? 1 : 0;
-    const int nout = p.act == 1 ? p.N / 2 : p.N;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    PT_CHECK(!(p.res_post && !p.res), "pt_igemm_f16: res_post without res");
-    PT_CHECK(!(p.res_lo && !p.res), "pt_igemm_f16: res_lo without res");
-    PT_CHECK(!(p.out_lo && (p.out_f32 || p.act == 1)), "pt_igemm_f16: out_lo needs an fp16, non-GEGLU output");
-    PT_CHECK(p.cs_cols >= 0 && p.cs_cols % 8 == 0, "pt_igemm_f16: cs_cols=%d must be a non-negative multiple of 8", p.cs_cols);
-    kp.vec_ok = !p.out_f32 && (nout % 8 == 0) && (p.ldo % 8 == 0) && al16(p.out) && (!p.res || (p.ldr % 8 == 0 && al16(p.res))) && al16(p.res_lo) && al16(p.out_lo) &&
-                (!p.vec || (p.ldv % 8 == 0 && al16(p.vec))) && (!p.blend || (p.ldb % 8 == 0 && al16(p.blend)));
-    const bool fast = (Ctot % BK == 0) && (p.C0 % BK == 0) && (p.Kpad == p.K);
-    const int force = g_force_cfg;
-    int cfg = force >= 0 ? force : choose_cfg(p.M, p.N, p.Kpad / BK, p.act, p.res || p.blend, fast);
-    int splits = (force < 0 || force == 3) ? plan_splits(p, fast, kp.vec_ok) : 1;
-    if (splits > 1 && !(p.splitk_ws && p.splitk_ws_bytes >= (int64_t)splits * p.M * p.N * 4)) splits = 1;   // no workspace offered
-    if (splits > 1) cfg = 3;
-    if (force < 0 && p.N <= 96 && p.act != 1 && splits == 1) cfg = 5;      // tools/micro/igemm_n32_sweep.py: 2.6-4 x on N = 16 / 32, 1.5 x on 96
-    if (cfg == 3 && !fast) cfg = p.act == 1 ? 0 : 1;         // the 256x320 kernel has no generic-K gather
-    PT_CHECK(!(cfg == 5 && p.act == 1), "pt_igemm_f16: the 256x32 configuration does not support GEGLU");
-    PT_CHECK(!(cfg == 1 && p.act == 1), "pt_igemm_f16: the 128x320 configuration does not support GEGLU");
-    const int bm = (cfg == 0 || cfg == 3 || cfg == 5) ? 256 : 128, bn = cfg == 0 ? 256 : (cfg == 2 ? 128 : (cfg == 4 ? 160 : (cfg == 5 ? 32 : 320)));
-    kp.tiles_m = (p.M + bm - 1) / bm;
-    kp.tiles_n = (p.N + bn - 1) / bn;
-    PT_CHECK((long long)kp.tiles_m * kp.tiles_n < (1ll << 31), "pt_igemm_f16: grid too large");
-    {
-        static const int gm_env = getenv("PT_IGEMM_GROUP_M") ? atoi(getenv("PT_IGEMM_GROUP_M")) : 0;   // tuning override
-        const double in_px = p.upsample2x ? p.M / 4.0 : (double)p.M * p.stride * p.stride;
-        kp.gm = gm_env > 0 ? (gm_env < kp.tiles_m ? gm_env : kp.tiles_m)
-                           : choose_group(kp.tiles_m, kp.tiles_n, in_px * Ctot * 2.0, (double)p.N * p.K * 2.0, (cfg == 2 || cfg == 4) ? 64 : 32);
-    }
-    hipStream_t s = (hipStream_t)stream;
+    kp.foldx = pl.foldx ? 1 : 0;
+    kp.vec_ok = pl.vec_ok;
+    kp.tiles_m = pl.tiles_m;
+    kp.tiles_n = pl.tiles_n;
+    kp.gm = pl.gm;
     kp.ws = nullptr; kp.splits = 1;
-    {
-        static const int dbg = getenv("PT_IGEMM_DBG") ? atoi(getenv("PT_IGEMM_DBG")) : 0;
-        kp.dbg = dbg;
-    }
+    kp.dbg = g_ablation;
+    hipStream_t s = (hipStream_t)stream;
     pt_prof_begin(0, s, 2.0 * (double)p.M * (double)p.N * (double)p.K);
-    static const int pipe8 = getenv("PT_IGEMM_PIPE8") ? atoi(getenv("PT_IGEMM_PIPE8")) : 1;   // 0: the plain 256x256 loop
-    if (splits > 1) {
+    if (pl.splits > 1) {
         KParams k1 = kp;                                     // pass 1: bare products into the fp32 slabs
-        k1.ws = (float*)p.splitk_ws; k1.splits = splits;
+        k1.ws = (float*)p.splitk_ws; k1.splits = pl.splits;
         k1.p.bias = nullptr; k1.p.res = nullptr; k1.p.res_lo = nullptr; k1.p.out_lo = nullptr; k1.p.vec = nullptr; k1.p.blend = nullptr; k1.p.vec_mode = 0; k1.p.act = 0;
         launch10(k1, s);
         KParams k2 = kp;                                     // pass 2: ordered sum + the whole epilogue
-        k2.ws = (float*)p.splitk_ws; k2.splits = splits;
+        k2.ws = (float*)p.splitk_ws; k2.splits = pl.splits;
         const long long work = (long long)p.M * (p.N / 8);
         long long blocks = (work + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k2);
-    } else if (cfg == 3) launch10(kp, s);
-    else if (cfg == 0 && fast && pipe8) launch8(kp, s);
-    else if (cfg == 0) launch<CfgBig>(kp, fast, s);
-    else if (cfg == 1) launch<CfgW320>(kp, fast, s);
-    else if (cfg == 4) launch<CfgN160>(kp, fast, s);
-    else if (cfg == 5) launch<CfgN32>(kp, fast, s);
-    else launch<CfgSmall>(kp, fast, s);
+    } else if (pl.cfg == 3) launch10(kp, s);
+    else if (pl.cfg == 0 && pl.fast) launch8(kp, s);
+    else if (pl.cfg == 0) launch<CfgBig, false>(kp, s);     // the plain loop for generic K
+    else if (pl.cfg == 1) launch<CfgW320>(kp, pl.fast, s);
+    else if (pl.cfg == 4) launch<CfgN160>(kp, pl.fast, s);
+    else if (pl.cfg == 5) launch<CfgN32>(kp, pl.fast, s);
+    else launch<CfgSmall>(kp, pl.fast, s);
     pt_prof_end(0, s);
     PT_LAUNCH_CHECK("pt_igemm_f16");
     return 0;

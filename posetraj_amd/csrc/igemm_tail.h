@@ -22,7 +22,7 @@ struct KParams {
     long long stamps_cap;
     float* ws;                    // split-K: fp32 partial sums [splits][M][N] (igemm10_kernel only), else null
     int splits;                   // K tiles are dealt to `splits` workgroups per output tile (1 = off)
-    int dbg;                      // tuning ablations (PT_IGEMM_DBG; results are wrong): 1 = no global stores, 2 = no epilogue
+    int dbg;                      // tuning ablations (pt_igemm_set_tuning; results are wrong): 1 = no global stores, 2 = no epilogue, 4 = no GELU
     int foldx;                    // one-column kernels (KW = 1, no x padding / stride / upsampling): the output column is folded
                                   // into the pixel base and the packed x coordinate stays 0, so the image may be wider than 16
                                   // bits (the VAE's (3,1,1) convolutions see the image (F, H*W): 589 824 columns at 576 x 1024)

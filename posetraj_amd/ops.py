@@ -4,7 +4,6 @@ otherwise - there is no CPU or eager-PyTorch fallback."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -16,7 +15,7 @@ from . import hip
 # fp16(v) + fp16(v - fp16(v)); GEMM operands and norms read the high half (the plain fp16 tensor), residual adds read
 # both.  Removes the one-rounding-per-block random walk that carries 0.98e-3 of the U-Net's 1.08e-3 rel-L2.
 WIDE_KINDS = frozenset(("sc", "xs", "rb"))                       # shortcut conv, spatial resnet output, resblock output
-WIDE_STREAM = os.environ.get("PT_WIDE_STREAM", "1") != "0"      # (0: A/B of its cost, tools/ab_bench.py)
+WIDE_STREAM = True                                              # (False: A/B of its cost, tools/ab_bench.py)
 
 
 # Explicit-destination writes (``igemm(out=...)``) per buffer address.  A wide-stream tensor remembers the count its buffer had
@@ -57,7 +56,7 @@ _raw_device = getattr(torch._C, "_cuda_getDevice", None)
 
 def _stream() -> int:
     """The current HIP stream of the current device as an integer handle.  Through torch's C entry points when they exist:
-    ``torch.cuda.current_stream()`` builds a Stream object and re-checks ``is_available()`` (an ``os.environ`` lookup) on every
+    ``torch.cuda.current_stream()`` builds a Stream object and re-checks ``is_available()`` (an environment lookup) on every
     call - 12 us, 4 500 times per training step (tools/micro/train_host_profile.py)."""
     if _raw_stream is not None and _raw_device is not None:
         return _raw_stream(_raw_device())
@@ -199,8 +198,8 @@ def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, ge
     return out
 
 
-FUSED_FFN = os.environ.get("PT_FUSED_FFN", "1") != "0"          # (0: the two-launch form everywhere - A/B of pt_ffn_geglu_f16)
-FUSED_PRE = os.environ.get("PT_FUSED_PRE", "1") != "0"          # the attention's output projection + residual + LayerNorm in that launch's prologue (0: three launches, A/B)
+FUSED_FFN = True                                                # (False: the two-launch form everywhere - A/B of pt_ffn_geglu_f16)
+FUSED_PRE = True                                                # the attention's output projection + residual + LayerNorm in that launch's prologue (False: three launches, A/B)
 
 
 def ffn_fusable(w1: Packed, w2: Packed) -> bool:
@@ -259,13 +258,20 @@ def ffn_geglu(x: torch.Tensor, w1: Packed, w2: Packed, *, res: Optional[torch.Te
     return out
 
 
-FUSED_LNLIN = os.environ.get("PT_FUSED_LNLIN", "1") != "0"      # LayerNorm + Q/K/V projection of the 320-channel level in one launch (0: two launches, A/B)
+FUSED_LNLIN = True                                              # LayerNorm + Q/K/V projection of the 320-channel level in one launch (False: two launches, A/B)
 
 
 def ln_linear_fusable(x: torch.Tensor, pw: Packed) -> bool:
     """pt_ln_linear_f16 serves LayerNorm -> bias-free linear layer where a workgroup holds whole rows in registers: K == 320."""
     return (FUSED_LNLIN and pw.K == 320 and pw.Kpad == 320 and pw.bias is None and pw.KH == 1 and pw.KW == 1 and not pw.geglu
             and not pw.silu and pw.N % 8 == 0 and x.dim() == 2 and x.shape[1] == 320 and getattr(x, "lo", None) is None)
+
+
+def dispatch_key() -> tuple:
+    """The current values of the module switches that choose which launches run (WIDE_STREAM, FUSED_FFN, FUSED_PRE,
+    FUSED_LNLIN, blocks.FF_CHUNK_BYTES): a captured graph is only valid for the values it was captured under."""
+    from . import blocks
+    return WIDE_STREAM, FUSED_FFN, FUSED_PRE, FUSED_LNLIN, blocks.FF_CHUNK_BYTES
 
 
 def ln_linear(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pw: Packed, eps: float = 1e-5, *, cs_cols: int = 0,

@@ -376,7 +376,7 @@ class StableVideoDiffusionPipelineControlNet:
         if use_graph:
             key = (Bc, F, tuple(x.shape[3:]), tuple(cond.shape), None if cam is None else tuple(cam.shape),
                    float(controlnet_cond_scale), id(self.unet), id(self.controlnet), self.unet._generation,
-                   self.controlnet._generation, bool(overlap_streams), getattr(_networks, '__name__', None))
+                   self.controlnet._generation, bool(overlap_streams), getattr(_networks, '__name__', None), ops.dispatch_key())
             gs = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
             if gs is None:
                 gs = dict(key=key, xin=torch.empty((2 * Bc, F, x.shape[3], x.shape[4], 8), dtype=torch.float16, device=dev),

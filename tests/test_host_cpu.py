@@ -502,28 +502,52 @@ def test_trainer_state_files_round_trip(tmp_path):
         b.params.load(b.params.flat, dict(sd, **{"conv_in.bias": torch.zeros(7)}))
 
 
-def test_the_python_restatement_of_the_tile_model_has_the_kernels_constants():
-    """tools/cfg_model_check.py scores choose_cfg / plan_splits against the committed sweeps on the CPU; it is only evidence while its
-    constants ARE the ones in csrc/igemm.hip.  Parsed from the source: the five rows of `pipelined[]` and the round-6 split rule."""
-    import importlib.util
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("cfg_model_check", os.path.join(root, "tools", "cfg_model_check.py"))
+def test_the_librarys_tile_plan_on_the_committed_sweeps(lib):
+    """tools/cfg_model_check.py asks the built library's own planner (pt_igemm_plan: choose_cfg + plan_splits, host only) for every
+    shape of the committed sweeps: it picks the fastest measured configuration for all but one of the 60 shapes."""
+    import contextlib, importlib.util, io
+    spec = importlib.util.spec_from_file_location("cfg_model_check", os.path.join(ROOT, "tools", "cfg_model_check.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    src = open(os.path.join(root, "posetraj_amd", "csrc", "igemm.hip")).read()
-    table = src[src.index("static const Opt pipelined[5]"):]
-    rows = re.findall(r"\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\}", table)[:5]
-    assert len(rows) == 5
-    for i, r in enumerate(rows):
-        assert [int(v) for v in r] == [int(v) for v in mod.OPTS[i]], (i, r, mod.OPTS[i])
-    m = re.search(r"\(\(p\.N \+ 127\) / 128\) >= (\d+) && nk <= (\d+)\) return 1;", src)
-    assert m and (int(m.group(1)), int(m.group(2))) == (mod.SPLIT["tiles128"], mod.SPLIT["max_nk_unsplit"])
-    assert re.search(r"tiles > 128 \|\| nk < (\d+)", src).group(1) == str(mod.SPLIT["min_nk"])
-    # and the model, scored on the committed sweeps, picks the fastest measured configuration for all but one of the 60 shapes
-    import contextlib, io
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        mod.main([os.path.join(root, "profiles", "r06", f"igemm_cfg_sweep_{w}_r06c.txt") for w in ("L", "M")])
+        mod.main([os.path.join(ROOT, "profiles", "r06", f"igemm_cfg_sweep_{w}_r06c.txt") for w in ("L", "M")])
     out = buf.getvalue()
     assert out.count("<- best") == 1, out[-2000:]
+
+
+def test_igemm_plan_and_workspace_query_agree_without_a_gpu(lib):
+    """pt_igemm_splitk_ws_bytes and pt_igemm_f16 share one planner: the workspace asked for is exactly what the plan splits into, and
+    a call that offers none (ops.igemm(..., splitk=False)) runs un-split.  Host only, fake pointers: nothing is dereferenced."""
+    import ctypes
+    from posetraj_amd import hip
+    p = hip.IgemmParams()
+    p.x0 = p.w = p.out = 1 << 20
+    M, N, K = 4032, 1280, 11520                                  # level 3's long reduction: split-K (profiles/r06)
+    p.C0, p.ld0, p.Nimg, p.Hin, p.Win, p.Hout, p.Wout, p.KH, p.KW, p.stride = K, K, M, 1, 1, 1, 1, 1, 1, 1
+    p.M, p.N, p.K, p.Kpad, p.ldo, p.out_scale = M, N, K, K, N, 1.0
+    cfg, splits, gm = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    plan = lambda: hip.check(lib.pt_igemm_plan(ctypes.byref(p), ctypes.byref(cfg), ctypes.byref(splits), ctypes.byref(gm)), "pt_igemm_plan")
+    plan()
+    assert splits.value == 1 and gm.value >= 1
+    need = lib.pt_igemm_splitk_ws_bytes(ctypes.byref(p))
+    p.splitk_ws, p.splitk_ws_bytes = 1 << 20, need
+    plan()
+    assert cfg.value == 3 and splits.value > 1 and need == splits.value * M * N * 4
+    p.splitk_ws_bytes = need - 1                                 # too small a workspace: un-split
+    plan()
+    assert splits.value == 1
+    p.Kpad = K + 8                                               # invalid: reported, no plan, no workspace
+    assert lib.pt_igemm_plan(ctypes.byref(p), None, None, None) != 0 and b"Kpad" in lib.pt_last_error()
+    assert lib.pt_igemm_splitk_ws_bytes(ctypes.byref(p)) == 0
+
+
+def test_product_behaviour_does_not_depend_on_the_environment():
+    """Which kernels run is chosen by explicit library hooks and module constants (ops.dispatch_key is part of the pipeline's graph
+    key), never by environment variables: a captured graph could not see those."""
+    csrc = os.path.join(ROOT, "posetraj_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if os.path.isfile(os.path.join(csrc, f)):
+            assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+    for f in ("posetraj_amd/ops.py", "posetraj_amd/blocks.py", "oracle/quant.py"):
+        assert "os.environ" not in open(os.path.join(ROOT, f)).read(), f

@@ -329,6 +329,37 @@ def test_hipgraph_is_reused_for_a_second_clip(dev):
     assert not torch.equal(res[0], res[1])
 
 
+def test_hipgraph_is_recaptured_when_a_dispatch_switch_flips(dev):
+    """The module switches of ops.dispatch_key are part of the graph key: flipping ops.FUSED_PRE between two denoise(use_graph=True)
+    calls captures a new graph, and each result equals the eager launches under its own setting (a stale replay would return the
+    other setting's result).  Tiny nets with a 320-channel first level, where the fused prologue serves the transformers."""
+    from posetraj_amd import EulerDiscreteScheduler, StableVideoDiffusionPipelineControlNet, SVD_SCHEDULER_CONFIG, ops
+    cfg = dict(P.TINY, block_out_channels=(320, 128, 256, 256), num_attention_heads=(5, 2, 4, 4))
+    cn_o, unet_o = P.build_oracle_nets(seed=14, cfg=cfg)
+    cn_h, unet_h = P.build_hip_nets(cn_o, unet_o, dev, cfg=cfg)
+    pipe = StableVideoDiffusionPipelineControlNet(unet=unet_h, controlnet=cn_h,
+                                                  scheduler=EulerDiscreteScheduler(**SVD_SCHEDULER_CONFIG))
+    g = torch.Generator().manual_seed(400)
+    lat = (torch.randn(1, 14, 4, 8, 8, generator=g) * 700).to(dev)
+    mode = torch.randn(1, 4, 8, 8, generator=g).half()
+    il = torch.cat([torch.zeros_like(mode), mode]).to(dev)
+    e = torch.randn(1, 1, 64, generator=g).half()
+    emb = torch.cat([torch.zeros_like(e), e]).to(dev)
+    c1 = (torch.rand(1, 14, 3, 64, 64, generator=g) * 2 - 1).half()
+    cond = torch.cat([c1, c1]).to(dev)
+    keep, outs, keys = ops.FUSED_PRE, {}, {}
+    try:
+        for on in (True, False):
+            ops.FUSED_PRE = on
+            outs[on] = pipe.denoise(lat, il, emb, cond, num_inference_steps=2, use_graph=True, overlap_streams=True)
+            keys[on] = pipe._graph_state["key"]
+            assert torch.equal(outs[on], pipe.denoise(lat, il, emb, cond, num_inference_steps=2, use_graph=False, overlap_streams=False)), on
+    finally:
+        ops.FUSED_PRE = keep
+    assert keys[True] != keys[False]
+    assert not torch.equal(outs[True], outs[False])           # the switch changes the launches: a stale replay would have shown
+
+
 @pytest.mark.parametrize("tag,dt", [("f32", torch.float32), ("f16", torch.float16)])
 def test_add_noise_matches_reference_golden(golden, dev, tag, dt):
     """EulerDiscreteScheduler.add_noise on the device, against the reference's outputs, bit for bit."""

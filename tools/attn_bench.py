@@ -7,9 +7,6 @@ import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-from posetraj_amd import hip
-if os.environ.get("PT_LIB"):
-    hip.LIB_PATH = os.path.abspath(os.environ["PT_LIB"])
 from posetraj_amd import ops
 import energy_table as ET
 ap = argparse.ArgumentParser(); ap.add_argument("--seconds", type=float, default=3.0); a = ap.parse_args()

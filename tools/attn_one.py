@@ -4,9 +4,6 @@ PT_LIB=<path> loads an experimental build of libposetraj_hip.so instead of the i
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from posetraj_amd import hip
-if os.environ.get("PT_LIB"):
-    hip.LIB_PATH = os.path.abspath(os.environ["PT_LIB"])
 from posetraj_amd import ops
 dev = torch.device("cuda:0")
 Nimg, S, heads = 28, 9216, 5

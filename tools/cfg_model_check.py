@@ -1,70 +1,47 @@
 #!/usr/bin/env python3
-"""The tile-configuration model of csrc/igemm.hip (choose_cfg + plan_splits, restated here) against the measured sweeps
-(tools/igemm_cfg_sweep.py tables): for every shape the configuration the model picks, what it costs against the best measured
-one, and the total regret weighted by how often the shape occurs in one loop iteration.  CPU only.
+"""The tile-configuration plan of the built library (pt_igemm_plan: choose_cfg + plan_splits of csrc/igemm.hip) against the
+measured sweeps (tools/igemm_cfg_sweep.py tables): for every shape the configuration the library picks, what it costs against the
+best measured one, and the total regret weighted by how often the shape occurs in one loop iteration.  CPU only: the planner is
+host code and touches no device.
 
-    python tools/cfg_model_check.py profiles/r06/igemm_cfg_sweep_L_r06c.txt profiles/r06/igemm_cfg_sweep_M_r06c.txt [loop4=2150 epi3=19000 tiles128=1000000000 ...]
-(the arguments in brackets restore round 5's constants: "shipped auto" in those tables was measured with them)
+    python tools/cfg_model_check.py profiles/r06/igemm_cfg_sweep_L_r06c.txt profiles/r06/igemm_cfg_sweep_M_r06c.txt
+A what-if calibration (other constants in choose_cfg / plan_splits) is an edit of csrc/igemm.hip and a rebuild; this tool builds the
+library when a source is newer than it.
 """
-import math, sys
+import ctypes as C
+import os
+import sys
 
-OPTS = {  # bm, bn, slots, pro, loop, epi, epi_geglu, epi_side        (csrc/igemm.hip: choose_cfg)
-    0: [256, 256, 256, 5000, 2650, 10500, 8700, 4000],
-    1: [128, 320, 256, 3000, 2330, 9000, 9000, 4000],
-    2: [128, 128, 512, 3000, 1900, 7000, 6000, 2000],
-    3: [256, 320, 256, 5500, 3300, 16000, 11720, 9000],
-    4: [128, 160, 512, 3000, 2430, 8000, 7000, 3000],
-}
-WAVE_W = {0: 128, 1: 80, 2: 64, 3: 160, 4: 160}
-SPLIT = dict(min_nk=48, tiles128=300, max_nk_unsplit=80)
-def choose(M, N, nk, geglu, side):
-    best, bt = 2, 1e300
-    for i, (bm, bn, slots, pro, loop, epi, epig, epis) in OPTS.items():
-        if i == 1 and geglu:
-            continue
-        tiles = math.ceil(M / bm) * math.ceil(N / bn)
-        rounds = math.ceil(tiles / slots)
-        tile = pro + nk * loop + (epig if geglu else epi) + (epis if side else 0)
-        ragged = 1.3 if (N > WAVE_W[i] and N % WAVE_W[i]) else 1.0
-        t = rounds * tile * ragged
-        if t < bt * 0.999:
-            bt, best = t, i
-    return best
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from posetraj_amd import hip
+
+FAKE = 1 << 20          # 16-byte-aligned stand-in for every device pointer: the planner never dereferences them
 
 
-def splits(M, N, nk, geglu):
-    if geglu or N % 8:
-        return 1
-    tiles = math.ceil(M / 256) * math.ceil(N / 320)
-    if tiles > 128 or nk < SPLIT["min_nk"]:
-        return 1
-    if math.ceil(M / 128) * math.ceil(N / 128) >= SPLIT["tiles128"] and nk <= SPLIT["max_nk_unsplit"]:
-        return 1
-    s = min(256 // tiles, nk // 6, 16)
-    if s < 2:
-        return 1
-    per = math.ceil(nk / s)
-    s = math.ceil(nk / per)
-    return 1 if s < 2 else s
+def plan(M, N, K, geglu, side):
+    """(configuration, split-K count) of pt_igemm_f16 for the linear layer [M, K] x [K, N] (N packed: GEGLU halves it)."""
+    p = hip.IgemmParams()
+    p.x0 = p.w = p.out = p.splitk_ws = FAKE
+    p.C0, p.ld0 = K, K
+    p.Nimg, p.Hin, p.Win, p.Hout, p.Wout, p.KH, p.KW, p.stride = M, 1, 1, 1, 1, 1, 1, 1
+    p.M, p.N, p.K, p.Kpad, p.ldo = M, N, K, K, N // 2 if geglu else N
+    p.act, p.out_scale = (1 if geglu else 0), 1.0
+    p.splitk_ws_bytes = 1 << 62                              # any workspace the plan asks for is on offer
+    if side:
+        p.res, p.ldr = FAKE, N
+    cfg, splits = C.c_int32(), C.c_int32()
+    hip.check(hip.lib().pt_igemm_plan(C.byref(p), C.byref(cfg), C.byref(splits), None), "pt_igemm_plan")
+    return cfg.value, splits.value
 
 
-def main(argv):
-    for a in argv:
-        if "=" in a:
-            k, v = a.split("=")
-            if k in SPLIT:
-                SPLIT[k] = int(v)
-            else:                                                 # e.g. loop4=2430  epi3=19000
-                name, c = k[:-1], int(k[-1])
-                OPTS[c][["bm", "bn", "slots", "pro", "loop", "epi", "epig", "epis"].index(name)] = float(v)
-
-
+def main(paths):
+    hip.build()
     # launches per loop iteration of the swept shapes (profiles/r05/igemm_shapes_L_r05z4.txt; the same layers at the M row counts)
     COUNT = {(2560, 320): 0, (960, 320): 14, (320, 320): 17, (320, 1280): 0, (5120, 640): 21, (1920, 640): 14, (640, 640): 28, (640, 2560): 21,
              (10240, 1280): 21, (3840, 1280): 14, (1280, 1280): 28, (1280, 5120): 21, (1280, 11520): 12, (320, 2880): 11, (640, 5760): 9,
              (320, 960): 14, (640, 1920): 14, (1280, 3840): 14, (1280, 23040): 2, (640, 11520): 1, (320, 5760): 2, (1280, 2560): 2}
     tot_auto = tot_best = tot_model = 0.0
-    for path in [a for a in argv if "=" not in a]:
+    for path in paths:
         print(f"== {path}")
         for line in open(path):
             parts = [c.strip() for c in line.split("|")]
@@ -77,9 +54,7 @@ def main(argv):
                 if cell != "-":
                     us[c] = float(cell.split("us")[0])
             auto = float(parts[6].split("us")[0])
-            nk = K // 64
-            s = splits(M, N, nk, g)
-            pick = 3 if s > 1 else choose(M, N, nk, g, r)
+            pick, s = plan(M, N, K, g, r)
             # a forced configuration 3 in the sweep was measured WITH the split plan of the shipped build; an un-split pick of 3 where
             # the shipped build splits (or the reverse) is not in the table: flagged
             best = min(us, key=us.get)

@@ -1,15 +1,13 @@
 #!/usr/bin/env python3
 """Times pt_igemm_f16 on the short-K / small-M shapes of the 14x576x1024 workload (hipEvents, median of N launches).
 
-    python tools/igemm_bench.py [--reps 20] [--cfg -1] [SHAPE ...]      SHAPE = M,N,K[,geglu[,res[,vec[,wide]]]]
-Library switches are read once per process (PT_IGEMM_*): run once per variant, e.g. under PT_LIB=<other .so>."""
+    python tools/igemm_bench.py [--reps 20] [--cfg -1] [--group-m 0] [--ablation 0] [SHAPE ...]      SHAPE = M,N,K[,geglu[,res[,vec[,wide]]]]
+--cfg / --group-m / --ablation go through the library's hooks (pt_igemm_force_config, pt_igemm_set_tuning; an ablation makes the
+results wrong); PT_LIB=<other .so> times another build."""
 import argparse, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from posetraj_amd import hip
-if os.environ.get("PT_LIB"):
-    hip.LIB_PATH = os.path.abspath(os.environ["PT_LIB"])
-from posetraj_amd import ops
+from posetraj_amd import hip, ops
 from posetraj_amd.packing import pack_linear
 
 DEFAULT = ["258048,2560,320,1", "258048,960,320", "258048,320,320,0,1,1", "258048,320,320,0,1", "258048,320,320",
@@ -18,11 +16,14 @@ DEFAULT = ["258048,2560,320,1", "258048,960,320", "258048,320,320,0,1,1", "25804
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--cfg", type=int, default=-1)
+ap.add_argument("--group-m", type=int, default=0)
+ap.add_argument("--ablation", type=int, default=0)
 ap.add_argument("shapes", nargs="*")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)
 hip.check(hip.lib().pt_igemm_force_config(a.cfg))
+hip.check(hip.lib().pt_igemm_set_tuning(a.group_m, a.ablation))
 tot = 0.0
 for sh in (a.shapes or DEFAULT):
     v = [int(t) for t in sh.split(",")] + [0, 0, 0, 0]

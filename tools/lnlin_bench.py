@@ -6,8 +6,6 @@ import argparse, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from posetraj_amd import hip, ops
-if os.environ.get("PT_LIB"):
-    hip.LIB_PATH = os.path.abspath(os.environ["PT_LIB"])
 from posetraj_amd.packing import pack_linear
 
 ap = argparse.ArgumentParser(); ap.add_argument("--rows", type=int, nargs="*", default=[258048, 80640]); ap.add_argument("--n", type=int, default=960)

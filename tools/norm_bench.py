@@ -3,9 +3,6 @@
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from posetraj_amd import hip
-if os.environ.get("PT_LIB"):
-    hip.LIB_PATH = os.path.abspath(os.environ["PT_LIB"])
 from posetraj_amd import ops
 
 dev = torch.device("cuda:0")

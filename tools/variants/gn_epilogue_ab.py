@@ -93,6 +93,7 @@ w = (torch.randn(C, C, 3, 3, generator=g) * (9 * C) ** -0.5)
 pw = pack_conv2d(w, torch.zeros(C), dev)
 res = torch.randn(N * H * W, C, generator=g).half().to(dev)
 hip.check(hip.lib().pt_igemm_force_config(3))
+hip.check(hip.lib().pt_igemm_set_tuning(0, int(sys.argv[1])))   # ablation bit 8 switches the variant's statistics on
 for _ in range(3):
     y = ops.igemm(x, pw, geom=(N, H, W), res=res, wide=True)
 torch.cuda.synchronize()
@@ -108,9 +109,9 @@ print("%%s  conv3x3 258048x320x2880 + res, wide: median %%.1f us  min %%.1f us" 
 
 def run():
     for rnd in range(3):
-        for tag, env in (("base   ", {}), ("variant", {"PT_LIB": LIB, "PT_IGEMM_DBG": "8"})):
+        for tag, env, ablation in (("base   ", {}, "0"), ("variant", {"PT_LIB": LIB}, "8")):
             e = dict(os.environ, TAG=f"round {rnd} {tag}", **env)
-            subprocess.run([sys.executable, "-c", CHILD % ROOT], env=e, check=True)
+            subprocess.run([sys.executable, "-c", CHILD % ROOT, ablation], env=e, check=True)
 
 
 if __name__ == "__main__":
