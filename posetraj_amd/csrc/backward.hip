@@ -30,8 +30,8 @@ __device__ __forceinline__ void fold_strip(float (*red)[256 * 2], const float* s
 // y = silu?(xh * gamma + beta), xh = (x - mean_g) * rstd_g over the (rows_per_sample x C/groups) elements of a group.
 //   g  = dy * silu'(z)                                   dgamma[c] += sum g xh      dbeta[c] += sum g
 //   dx = rstd (g gamma - (s1 + xh s2) / n),  s1 = sum_group g gamma,  s2 = sum_group g gamma xh
-// stat[sample][group][4] = (sum x, sum x^2, s1, s2) in fp32.  Three passes: MODE 0 (x statistics), MODE 1 (s1, s2 and the
-// parameter gradients), apply.  grid (slabs, strips, samples).
+// stat[sample][group][4] = (sum x - P_g, sum (x - P_g)^2, s1, s2) in fp32, P_g the group's pivot (pt_gn_pivot: mean = P_g + S / n).
+// Three passes: MODE 0 (x statistics), MODE 1 (s1, s2 and the parameter gradients), apply.  grid (slabs, strips, samples).
 template <int MODE>
 __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__ x0, const f16* __restrict__ x1, int C0, int C1, int groups,
                                                          int64_t rows_per_sample, int rows_per_slab, float eps,
@@ -52,17 +52,19 @@ __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__
         const int64_t r0 = (int64_t)slab * rows_per_slab;
         int64_t r1 = r0 + rows_per_slab; if (r1 > rows_per_sample) r1 = rows_per_sample;
         const int64_t row_base = (int64_t)sample * rows_per_sample;
-        float mean[8], rstd[8], ga[8], be[8];
+        float mean[8], rstd[8], ga[8], be[8], pv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pv[j] = pt_gn_pivot(x0, x1, C0, C1, rows_per_sample, sample, (c + j) / cg * cg);
         if (MODE == 1) {
             const double cnt = (double)rows_per_sample * cg;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int g = (c + j) / cg;
                 const float* st = stat + ((int64_t)sample * groups + g) * 4;
-                const double m = (double)st[0] / cnt;
-                double var = (double)st[1] / cnt - m * m;
+                const double d = (double)st[0] / cnt;
+                double var = (double)st[1] / cnt - d * d;
                 if (var < 0.0) var = 0.0;
-                mean[j] = (float)m; rstd[j] = (float)(1.0 / sqrt(var + (double)eps));
+                mean[j] = (float)((double)pv[j] + d); rstd[j] = (float)(1.0 / sqrt(var + (double)eps));
                 ga[j] = (float)gamma[c + j]; be[j] = (float)beta[c + j];
             }
         }
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__
             const f16x8 v = *(const f16x8*)(src + (row_base + r) * ld + co);
             if (MODE == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; s[j] += f; q[j] += f * f; }
+                for (int j = 0; j < 8; ++j) { const float f = (float)v[j] - pv[j]; s[j] += f; q[j] += f * f; }
             } else {
                 const f16x8 d = *(const f16x8*)(dy + (row_base + r) * Ct + c);
 #pragma unroll
@@ -129,10 +131,11 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const f16* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float* st = stat + ((int64_t)sample * groups + (c + j) / cg) * 4;
-        const double m = (double)st[0] / cnt;
-        double var = (double)st[1] / cnt - m * m;
+        const double d = (double)st[0] / cnt;
+        double var = (double)st[1] / cnt - d * d;
         if (var < 0.0) var = 0.0;
-        mean[j] = (float)m; rstd[j] = (float)(1.0 / sqrt(var + (double)eps));
+        mean[j] = (float)((double)pt_gn_pivot(x0, x1, C0, C1, rows_per_sample, sample, (c + j) / cg * cg) + d);
+        rstd[j] = (float)(1.0 / sqrt(var + (double)eps));
         ga[j] = (float)gamma[c + j]; be[j] = (float)beta[c + j];
         k1[j] = (float)((double)st[2] / cnt); k2[j] = (float)((double)st[3] / cnt);
     }
@@ -189,13 +192,16 @@ __global__ __launch_bounds__(256) void lnb_kernel(const f16* __restrict__ x, int
                 xv[u] = *(const f16x8*)(xr + ch * 8);
                 dv[u] = *(const f16x8*)(dr + ch * 8);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)xv[u][j]; s += f; q += f * f; }
+                for (int j = 0; j < 8; ++j) s += (float)xv[u][j];
             }
         }
-        s = pt_wave_sum(s); q = pt_wave_sum(q);
-        const float mean = s / C;
-        float var = q / C - mean * mean; if (var < 0.f) var = 0.f;
-        const float rstd = 1.0f / sqrtf(var + eps);
+        const float mean = pt_wave_sum(s) / C;
+#pragma unroll
+        for (int u = 0; u < LN_MAXCH; ++u)                  // two passes over the registers: the centred variance (q / C - mean^2
+            if (lane + 64 * u < CH)                          // from fp32 sums lost it at ~100 sigma, tests/test_norm_numerics_gpu.py)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const float d = (float)xv[u][j] - mean; q += d * d; }
+        const float rstd = 1.0f / sqrtf(pt_wave_sum(q) / C + eps);
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int u = 0; u < LN_MAXCH; ++u) {
@@ -266,14 +272,20 @@ __global__ __launch_bounds__(256) void lnb_narrow_kernel(const f16* __restrict__
                 xv[u] = *(const f16x8*)(x + r * C + ch * 8);
                 dv[u] = *(const f16x8*)(dy + r * C + ch * 8);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)xv[u][j]; s += f; q += f * f; }
+                for (int j = 0; j < 8; ++j) s += (float)xv[u][j];
             }
         }
 #pragma unroll
-        for (int o = 1; o < LPR; o <<= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+        for (int o = 1; o < LPR; o <<= 1) s += __shfl_xor(s, o);
         const float mean = s * invC;
-        float var = q * invC - mean * mean; if (var < 0.f) var = 0.f;
-        const float rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+        for (int u = 0; u < NCH; ++u)                       // the centred variance, second pass over the registers (as lnb_kernel)
+            if (ok && li + LPR * u < CH)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const float d = (float)xv[u][j] - mean; q += d * d; }
+#pragma unroll
+        for (int o = 1; o < LPR; o <<= 1) q += __shfl_xor(q, o);
+        const float rstd = 1.0f / sqrtf(q * invC + eps);
         if (PARAMS && ok && li == 0) *(f32x2*)(rowstat + 2 * r) = f32x2{mean, rstd};
         float a = 0.f, b = 0.f;
 #pragma unroll

@@ -9,8 +9,8 @@
 //
 //   Workgroup = 128 rows, 8 waves as 4 row pairs (32 rows each) x 2 halves (s).  Prologue: each wave loads its pair's 32 rows x 320
 //   channels straight into B-operand fragments (80 VGPRs; a row's 320 channels sit in 4 lanes, both waves of a pair hold the same
-//   rows), takes the row sums and sums of squares from 40 MFMAs on those very fragments (ones . X^T and the diagonal of X . X^T: the
-//   VALU form cost 6.7 us per workgroup) and rewrites the fragments as y = (x - mean) * rstd * gamma + beta rounded to fp16 - the value
+//   rows), takes the row sums and sums of squares from 40 MFMAs on those very fragments (ones . X^T and the diagonal of X . X^T, 40 more
+//   on centred fragments in a wave that holds a row far off zero; the VALU form cost 6.7 us per workgroup) and rewrites the fragments as y = (x - mean) * rstd * gamma + beta rounded to fp16 - the value
 //   pt_layernorm_f16 would have stored, up to the summation order of the statistics.
 //   The N output columns are walked in chunks of 128 weight rows (64 per half s): five 64-deep K tiles of 16 KiB each come through
 //   LDS by LDS-DMA into a TEN-slot ring (two whole chunks, all of the CU's 160 KiB: slot = (chunk parity, K tile)), each slot refilled
@@ -107,8 +107,14 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
     //   D = ones . X^T : every row of D is sum_k x[pixel][k] - each lane reads its pixel's sum in D[.][frow];
     //   D = X . X^T    : A and B operands share one register layout, and the DIAGONAL D[p][p] = sum_k x[p][k]^2 (fp16 products are exact in
     //                    fp32, fp32 accumulation) sits in lane (frow = p, fq = p >> 2), element p & 3 - fetched by the pixel's other lanes.
-    // var = E[x^2] - mean^2 in fp32 (hidden states are centred to within a few sigma; the two-pass form of pt_layernorm_f16 differs from
-    // this by ~1e-6 relative in rstd, an fp16 ulp on isolated outputs).
+    // var = E[x^2] - mean^2 in fp32 is exact enough while |mean| / sigma < 8 (hidden states are centred to within a few sigma).  A row
+    // beyond that - an offset row, a constant or near-constant one - lost its variance (rstd wrong by 5e-3 at 100 sigma, by 5e-2 at 300, and
+    // 1 / sqrt(eps) times an fp32 rounding of the mean instead of beta on a constant row: tests/test_norm_numerics_gpu.py).  When a wave holds
+    // such a row, it runs the two MFMAs once more on fragments centred on P = fp16(mean): x - P is exact in fp16 wherever x lies within a
+    // factor of two of P, which holds for every value within |mean| / 2 of the mean; mean = P + S / 320, var = Q / 320 - (S / 320)^2 with
+    // S, Q of the order of sigma.  Rows inside the bound keep the one-pass values (a fp16 centring rounds where x and P straddle zero and
+    // cost those rows 1e-4 of relative error), and waves without such a row skip the second pass.  The two-pass form of pt_layernorm_f16
+    // differs from this by an fp16 ulp on isolated outputs.
     float mean[2], rstd[2];
     {
         const f16x8 ones = {(f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f};
@@ -122,10 +128,27 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
                 q4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Xf[r][tt], Xf[r][tt], q4, 0, 0, 0);
             }
             const int j = frow & 3;
-            const float dg = j == 0 ? q4[0] : (j == 1 ? q4[1] : (j == 2 ? q4[2] : q4[3]));
-            const float sq = __shfl(dg, diag_lane);
-            mean[r] = s4[0] * (1.0f / 320.0f);
-            rstd[r] = rsqrtf(fmaxf(sq * (1.0f / 320.0f) - mean[r] * mean[r], 0.f) + lp.eps);
+            float dg = j == 0 ? q4[0] : (j == 1 ? q4[1] : (j == 2 ? q4[2] : q4[3]));
+            float m = s4[0] * (1.0f / 320.0f);
+            float var = __shfl(dg, diag_lane) * (1.0f / 320.0f) - m * m;
+            const bool far = m * m > 64.0f * var;            // |mean| / sigma > 8, or no variance left at all (all-zero rows excepted)
+            if (__ballot(far)) {                             // (wave-uniform: every lane takes part in the MFMAs and the shuffle)
+                const f16 p = (f16)m;
+                const f16x8 p8 = {p, p, p, p, p, p, p, p};
+                s4 = (f32x4){0.f, 0.f, 0.f, 0.f}; q4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int tt = 0; tt < 10; ++tt) {
+                    const f16x8 d = Xf[r][tt] - p8;
+                    s4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, d, s4, 0, 0, 0);
+                    q4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(d, d, q4, 0, 0, 0);
+                }
+                dg = j == 0 ? q4[0] : (j == 1 ? q4[1] : (j == 2 ? q4[2] : q4[3]));
+                const float dm = s4[0] * (1.0f / 320.0f);    // mean - P
+                const float dv = __shfl(dg, diag_lane) * (1.0f / 320.0f) - dm * dm;
+                if (far) { m = (float)p + dm; var = dv; }
+            }
+            mean[r] = m;
+            rstd[r] = rsqrtf(fmaxf(var, 0.f) + lp.eps);
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // (gamma / beta of waves 5 and 6 have landed; so has everything else)

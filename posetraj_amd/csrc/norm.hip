@@ -6,9 +6,10 @@ namespace {
 
 // ------------------------------------------------------------------------------------------ GroupNorm stats
 // grid (slabs, strips, samples).  A strip is 256 consecutive channels (32 chunks of 8), a slab a run of rows.
-// Thread (ty, tx): chunk column tx of the strip, rows ty, ty+8, ...  -> 16 fp32 accumulators in registers, folded to
-// per-channel and then per-group sums inside the block; each block writes its <= 34 group sums (the groups its strip
-// touches) to part[sample][slab][strip][GN_SLOTS][2]; the apply pass folds them (gn_fold_sample): bit-reproducible, no atomics.
+// Thread (ty, tx): chunk column tx of the strip, rows ty, ty+8, ...  -> 16 fp32 accumulators of x - P_g and (x - P_g)^2 (P_g the
+// group's pivot, pt_gn_pivot) in registers, folded to per-channel and then per-group sums inside the block; each block writes its
+// <= 34 group sums (the groups its strip touches) to part[sample][slab][strip][GN_SLOTS][2]; the apply pass folds them
+// (gn_fold_sample): bit-reproducible, no atomics.
 constexpr int GN_TX = 32, GN_TY = 8, GN_SLOTS = 36;
 
 __global__ __launch_bounds__(256) void gn_partial_kernel(const f16* __restrict__ x0, const f16* __restrict__ x1,
@@ -18,12 +19,15 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const f16* __restrict__
     __shared__ float chan[256 * 2];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int slab = blockIdx.x, strip = blockIdx.y, sample = blockIdx.z;
-    const int Ctot = C0 + C1;
+    const int Ctot = C0 + C1, cg = Ctot / groups;
     const int c = strip * 256 + tx * 8;
     float s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
     if (c < Ctot) {
+        float pv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pv[j] = pt_gn_pivot(x0, x1, C0, C1, rows_per_sample, sample, (c + j) / cg * cg);
         const f16* src; int ld, co;
         if (c < C0) { src = x0; ld = C0; co = c; } else { src = x1; ld = C1; co = c - C0; }
         const int64_t r0 = (int64_t)slab * rows_per_slab;
@@ -37,12 +41,12 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const f16* __restrict__
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[u][j]; s[j] += f; q[j] += f * f; }
+                for (int j = 0; j < 8; ++j) { const float f = (float)v[u][j] - pv[j]; s[j] += f; q[j] += f * f; }
         }
         for (; r < r1; r += GN_TY) {
             const f16x8 v = *(const f16x8*)(base + r * ld);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; s[j] += f; q[j] += f * f; }
+            for (int j = 0; j < 8; ++j) { const float f = (float)v[j] - pv[j]; s[j] += f; q[j] += f * f; }
         }
     }
 #pragma unroll
@@ -56,7 +60,6 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const f16* __restrict__
     }
     __syncthreads();
     // groups touched by this strip: channels [c_lo, c_hi)
-    const int cg = Ctot / groups;
     const int c_lo = strip * 256, c_hi = (c_lo + 256 < Ctot) ? c_lo + 256 : Ctot;
     const int g_lo = c_lo / cg, g_hi = (c_hi - 1) / cg;
     const int ng = g_hi - g_lo + 1;
@@ -71,20 +74,23 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const f16* __restrict__
     }
 }
 
-// per sample: fold the per-block group partials in a fixed order -> mean / rstd of every group in LDS (grp[2 g], [2 g + 1]).
+// per sample: fold the per-block group partials in a fixed order -> the pivot P_g, mean - P_g and rstd of every group in LDS
+// (grp[4 g], [4 g + 1], [4 g + 2]).
 // 8 threads per group (256 threads = 32 groups at once), each summing every 8th slab, then a fixed-order fold over the 8:
 // all the loads of a thread are independent and in flight together.  Every block of gn_apply_kernel runs this for its
 // sample (same order, same bits in every block) instead of a finalize launch of its own (28 blocks, latency-bound:
 // 11-15 us per GroupNorm, 1.7 ms per denoise iteration), and instead of the in-launch fold by the last-arriving block
 // of round 2's first form (agent-scope ticket + release per block: 45-62 us per GroupNorm against 19 us for the bare
 // partial pass, profiles/r02/rocprofv3_kernel_stats_L_2iters_r02a.csv / _r02b.csv).
-__device__ __forceinline__ void gn_fold_sample(const float* __restrict__ part, int sample, int nslabs, int nstrips,
-                                               int Ctot, int groups, int64_t rows_per_sample, float eps, float* grp) {
-    const int cg = Ctot / groups;
+__device__ __forceinline__ void gn_fold_sample(const float* __restrict__ part, const f16* __restrict__ x0, const f16* __restrict__ x1,
+                                               int C0, int C1, int sample, int nslabs, int nstrips, int groups,
+                                               int64_t rows_per_sample, float eps, float* grp) {
+    const int Ctot = C0 + C1, cg = Ctot / groups;
     const int sub = threadIdx.x & 7;
     for (int g = threadIdx.x >> 3; g < groups; g += blockDim.x >> 3) {
         float s = 0.f, q = 0.f;
         const int ch0 = g * cg, ch1 = ch0 + cg - 1;
+        const float pg = pt_gn_pivot(x0, x1, C0, C1, rows_per_sample, sample, ch0);   // (in flight with the partials, not behind them)
         for (int strip = ch0 / 256; strip <= ch1 / 256; ++strip) {       // the 1-2 strips this group lives in
             const int g_lo = (strip * 256) / cg;
             const float* base = part + ((int64_t)sample * nslabs * nstrips + strip) * GN_SLOTS * 2 + (g - g_lo) * 2;
@@ -104,11 +110,12 @@ __device__ __forceinline__ void gn_fold_sample(const float* __restrict__ part, i
         for (int o = 1; o < 8; o <<= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
         if (sub == 0) {
             const double cnt = (double)rows_per_sample * cg;
-            const double mean = (double)s / cnt;
-            double var = (double)q / cnt - mean * mean;
+            const double d = (double)s / cnt;                // mean - P_g
+            double var = (double)q / cnt - d * d;
             if (var < 0.0) var = 0.0;
-            grp[2 * g] = (float)mean;
-            grp[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
+            grp[4 * g] = pg;
+            grp[4 * g + 1] = (float)d;
+            grp[4 * g + 2] = (float)(1.0 / sqrt(var + (double)eps));
         }
     }
 }
@@ -118,26 +125,30 @@ __device__ __forceinline__ void gn_fold_sample(const float* __restrict__ part, i
 // the chunk index advances without any division (the first version divided two 64-bit indices per 16-byte chunk and was
 // bound by that arithmetic, not by HBM: 2.8-4.4 TB/s).  Thread t starts at chunk t of the block's [rows x C/8] range and
 // steps by 256 chunks: (row, column) advance by the constant (256 / CH, 256 % CH) with one carry.
+// y = (x - P_g) a + b with a = rstd gamma, b = beta - (mean - P_g) a: x - P_g is exact in fp32, so no large a x and b cancel
+// (in a x + (beta - mean a) at 300 sigma, or on a constant group with rstd = 1 / sqrt(eps), they did) and a constant group gives beta.
 __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x0, const f16* __restrict__ x1, int C0,
                                                        int C1, int rows_per_sample, int rows_per_block,
                                                        const float* __restrict__ part, int nslabs, int nstrips, int groups,
                                                        float eps, const f16* __restrict__ gamma, const f16* __restrict__ beta,
                                                        int silu, f16* __restrict__ y) {
-    extern __shared__ __attribute__((aligned(16))) float s_ab[];          // [Ctot][2]: a = rstd*gamma, b = beta - mean*a
-    __shared__ float grp[2 * 64];
+    extern __shared__ __attribute__((aligned(16))) float s_ab[];          // [Ctot][2]: a = rstd*gamma, b = beta - (mean - P_g)*a; then P_g [Ctot] fp16
+    __shared__ float grp[4 * 32];
     const int Ctot = C0 + C1, CH = Ctot >> 3;
+    f16* const s_pv = (f16*)(s_ab + 2 * Ctot);
     const int sample = blockIdx.y;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(r0 + rows_per_block, rows_per_sample);
-    gn_fold_sample(part, sample, nslabs, nstrips, Ctot, groups, rows_per_sample, eps, grp);
+    gn_fold_sample(part, x0, x1, C0, C1, sample, nslabs, nstrips, groups, rows_per_sample, eps, grp);
     __syncthreads();
     {
         const int cg = Ctot / groups;
         for (int c = threadIdx.x; c < Ctot; c += 256) {
             const int g = c / cg;
-            const float a = grp[2 * g + 1] * (float)gamma[c];
+            const float a = grp[4 * g + 2] * (float)gamma[c];
             s_ab[2 * c] = a;
-            s_ab[2 * c + 1] = (float)beta[c] - grp[2 * g] * a;
+            s_ab[2 * c + 1] = (float)beta[c] - grp[4 * g + 1] * a;
+            s_pv[c] = (f16)grp[4 * g];
         }
     }
     __syncthreads();
@@ -156,11 +167,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
     auto finish = [&](int rw, int cc, const f16x8& v) {
         const int ch = cc * 8;
         const f32x4* abp = (const f32x4*)(s_ab + ch * 2);
+        const f16x8 pv = *(const f16x8*)(s_pv + ch);
         f16x8 o;
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             const f32x4 k = abp[h];                       // a0 b0 a1 b1
-            float u0 = (float)v[2 * h] * k[0] + k[1], u1 = (float)v[2 * h + 1] * k[2] + k[3];
+            float u0 = ((float)v[2 * h] - (float)pv[2 * h]) * k[0] + k[1], u1 = ((float)v[2 * h + 1] - (float)pv[2 * h + 1]) * k[2] + k[3];
             if (silu) { u0 = pt_silu(u0); u1 = pt_silu(u1); }
             o[2 * h] = (f16)u0; o[2 * h + 1] = (f16)u1;
         }
@@ -357,7 +369,7 @@ extern "C" int pt_groupnorm_apply(const void* x0, const void* x1, int32_t C0, in
     const int64_t min_rows = (256 * min_chunks + (Ctot >> 3) - 1) / (Ctot >> 3);
     if (rows_per_block < min_rows) rows_per_block = min_rows;
     const unsigned bx = (unsigned)((rows_per_sample + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(bx, (unsigned)n_samples), dim3(256), (size_t)Ctot * 8, (hipStream_t)stream,
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(bx, (unsigned)n_samples), dim3(256), (size_t)Ctot * 10, (hipStream_t)stream,
                        (const f16*)x0, (const f16*)x1, C0, C1, (int)rows_per_sample, (int)rows_per_block, partials, nslabs,
                        nstrips, groups, eps, (const f16*)gamma, (const f16*)beta, silu, (f16*)y);
     PT_LAUNCH_CHECK("pt_groupnorm_apply");

@@ -106,6 +106,16 @@ __device__ __forceinline__ float pt_wave_sum(float v) {
     return v;
 }
 
+// GroupNorm statistics are sums of x - P_g, not of x: E[x^2] - mean^2 from fp32 sums cancels to nothing once |mean| / sigma
+// reaches ~100 (an fp16 activation at 300 sigma carries no variance in fp32 sums of its squares).  The pivot P_g of a group is
+// its first element, x[sample, row 0, first channel of the group] - one fp16 value that every block of every pass reads alike;
+// then mean = P_g + S / n and var = Q / n - (S / n)^2 with S, Q of the order of sigma (tests/test_norm_numerics_gpu.py).
+// x0 [.., C0] and x1 [.., C1] are the two sources of a concatenation (channel ch of the group may lie in either).
+__device__ __forceinline__ float pt_gn_pivot(const f16* x0, const f16* x1, int C0, int C1, int64_t rows_per_sample, int sample, int ch) {
+    const int64_t r = (int64_t)sample * rows_per_sample;
+    return ch < C0 ? (float)x0[r * C0 + ch] : (float)x1[r * C1 + (ch - C0)];
+}
+
 // XCD-aware bijective remap of a linear workgroup id: workgroups that share an XCD (id % 8 equal under the
 // round-robin dispatch) get a contiguous chunk of the tile space, so neighbouring tiles hit the same L2.
 __device__ __forceinline__ int pt_xcd_remap(int bid, int nwg) {

@@ -167,8 +167,10 @@ __global__ __launch_bounds__(256) void groupnorm_f32_apply_kernel(const float* _
         const int c = (int)(i % C);
         const long long n = i / ((long long)rows * C);
         const double* st = stats + 2 * (n * groups + c / cpg);
-        const float mean = (float)st[0], rstd = (float)(1.0 / sqrt(st[1] + (double)eps));
-        float v = (x[i] - mean) * rstd * gamma[c] + beta[c];
+        // the fp64 mean as two floats: x - hi is exact near the mean, so a group far off zero (|mean| / sigma of 100s) keeps its
+        // centring; one float mean lost |mean| 2^-24 rstd gamma there (2e-4 on near-constant groups, tests/test_norm_numerics_gpu.py)
+        const float mhi = (float)st[0], mlo = (float)(st[0] - (double)mhi), rstd = (float)(1.0 / sqrt(st[1] + (double)eps));
+        float v = ((x[i] - mhi) - mlo) * rstd * gamma[c] + beta[c];
         if (silu) v = v / (1.0f + expf(-v));
         y[i] = v;
     }
