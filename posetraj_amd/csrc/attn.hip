@@ -21,16 +21,6 @@ constexpr int KB = 64, HD = 64;
 constexpr int KV_TILE = KB * HD * 2;          // 8 KiB
 constexpr int OROW = 144;                     // bytes per staged output row (128 + 16 pad)
 
-typedef f16 f16x4v __attribute__((ext_vector_type(4)));
-
-typedef __fp16 hw_f16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-// ds_read_b64_tr_b16: per 16-lane group a 4-row x 16-column block of halfs, delivered column-major
-__device__ __forceinline__ f16x4v lds_tr16(const char* p) {
-    const hw_f16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hw_f16x4*)p);
-    return __builtin_bit_cast(f16x4v, v);
-}
-
 // Softmax bookkeeping.
 //   * reference max instead of running max: scores leave the MFMA already relative to m_ref (the chains' C operand holds -m_ref),
 //     m_ref is only re-based when some query's tile maximum exceeds it by more than THR (defer-max, guide T13) - always in tile 0,
@@ -40,14 +30,7 @@ __device__ __forceinline__ f16x4v lds_tr16(const char* p) {
 //     pt_igemm_f16), so p = exp2(score) with no VALU op between the MFMA and v_exp_f32.  Otherwise p = exp2(score * c).
 // Workgroup order: all query blocks of one (image, head) run on ONE XCD (ids equal mod 8), so its K/V (2.4 MB at
 // S = 9216) are fetched into one L2 instead of eight.
-// Cross-lane exchanges (only in the re-base path) without LDS: v_permlane32_swap exchanges the upper half of its first operand with
-// the lower half of its second (v_permlane16_swap: odd rows of 16 lanes with even rows), so with both operands holding v the two
-// registers hold {own, partner's} in every lane.  Written as inline asm: through __builtin_amdgcn_permlane32_swap hipcc (ROCm 7.2)
-// used result 0 for both elements of the returned pair (max(r0, r1) compiled to r0 - every lane silently kept only the LOWER
-// lane's value).  The s_nop covers the VALU-write -> permlane-read hazard (2 wait states) inside the statement.
-__device__ __forceinline__ void pair_swap(float& a, float& b) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
+// Cross-lane exchanges (only in the re-base path) go through pt_swap16 / pt_swap32 (pt_common.h), without LDS.
 
 // The tile on v_mfma_f32_16x16x32_f16 (round 5; rounds 1-4 ran the same tile and schedule on 32x32x16, one query per lane pair): on
 // random data under the power cap the 16x16x32 shape holds a 13 % higher clock at equal cycles per flop
@@ -64,15 +47,12 @@ __device__ __forceinline__ void pair_swap(float& a, float& b) {
 //   row sums: A = ones: every row of D is the sum over the step's 32 keys, so all four registers of lacc[qb] hold l[q]
 // The steady state has no cross-lane step: `__any` over the lanes' LOCAL maxima is the wave's test; only a re-base combines the four
 // lanes of a query (v_permlane16_swap + v_permlane32_swap).
-__device__ __forceinline__ void quad_swap16(float& a, float& b) {      // rows of 16 lanes: a's odd rows <-> b's even rows
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
 __device__ __forceinline__ float query_max(float v) {                  // max over the four lanes l % 16 + 16 g
     float a = v, b = v;
-    quad_swap16(a, b);
+    pt_swap16(a, b);
     v = fmaxf(a, b);
     a = v; b = v;
-    pair_swap(a, b);
+    pt_swap32(a, b);
     return fmaxf(a, b);
 }
 
@@ -183,8 +163,8 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
         for (int db = 0; db < 4; ++db)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const f16x4v lo = lds_tr16(Vs + s * 4096 + voff[db][0]);
-                const f16x4v hi = lds_tr16(Vs + s * 4096 + voff[db][1]);
+                const f16x4 lo = pt_lds_tr16(Vs + s * 4096 + voff[db][0]);
+                const f16x4 hi = pt_lds_tr16(Vs + s * 4096 + voff[db][1]);
                 vf[db][s] = (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
         // the next tile's copies are issued behind every LDS read of this one: hipcc drains the LDS-DMA queue (vmcnt(0)) in front of a
@@ -267,13 +247,13 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
         const float inv = 1.0f / lacc[qb][0];
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-            f16x4v o4;
+            f16x4 o4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o4[j] = (f16)(ot[db][qb][j] * inv);
-            *(f16x4v*)(Os + (16 * qb + q16) * OROW + (16 * db + 4 * g) * 2) = o4;
+            *(f16x4*)(Os + (16 * qb + q16) * OROW + (16 * db + 4 * g) * 2) = o4;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
 #pragma unroll
     for (int pass = 0; pass < 2 * NQB; ++pass) {
         const int r = pass * 8 + (lane >> 3), c = lane & 7;
@@ -364,7 +344,7 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const f16* __restric
         for (int kb = 0; kb < NB; ++kb) pt[kb][qb] = (f16x4){(f16)p[kb][0], (f16)p[kb][1], (f16)p[kb][2], (f16)p[kb][3]};
     }
     // ---- O^T[d][q] = sum_k V[k][d] P^T[k][q]
-    __builtin_amdgcn_s_waitcnt(0xC07F);                      // this wave's V rows are in LDS
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));               // this wave's V rows are in LDS
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int blk = 0; blk < HDIM / 16; ++blk) {

@@ -20,13 +20,6 @@
 
 namespace {
 
-typedef f16 f16x4b __attribute__((ext_vector_type(4)));
-typedef __fp16 hw_f16x4b __attribute__((__vector_size__(4 * sizeof(__fp16))));
-__device__ __forceinline__ f16x4b ab_lds_tr16(const char* p) {
-    const hw_f16x4b v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hw_f16x4b*)p);
-    return __builtin_bit_cast(f16x4b, v);
-}
-
 constexpr int AB_T = 32;        // rows per streamed tile
 constexpr int AB_B = 64;        // stationary rows per workgroup (4 waves x 16)
 
@@ -144,8 +137,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const f16* __restri
             }
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4b lo = ab_lds_tr16(kfragt + db * 32);
-            const f16x4b hi = ab_lds_tr16(kfragt + 16 * PITCH + db * 32);
+            const f16x4 lo = pt_lds_tr16(kfragt + db * 32);
+            const f16x4 hi = pt_lds_tr16(kfragt + 16 * PITCH + db * 32);
             const f16x8 kt8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             dqt[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kt8, dsf, dqt[db], 0, 0, 0);
         }
@@ -159,8 +152,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const f16* __restri
         f16* op = dq + grow * lddq + hcol + 4 * g;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4b o4 = {(f16)(dqt[db][0] * scale), (f16)(dqt[db][1] * scale), (f16)(dqt[db][2] * scale), (f16)(dqt[db][3] * scale)};
-            *(f16x4b*)(op + db * 16) = o4;
+            const f16x4 o4 = {(f16)(dqt[db][0] * scale), (f16)(dqt[db][1] * scale), (f16)(dqt[db][2] * scale), (f16)(dqt[db][3] * scale)};
+            *(f16x4*)(op + db * 16) = o4;
         }
     }
 }
@@ -269,10 +262,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const f16* __restr
         }
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4b olo = ab_lds_tr16(ofragt + db * 32), ohi = ab_lds_tr16(ofragt + 16 * PITCH + db * 32);
+            const f16x4 olo = pt_lds_tr16(ofragt + db * 32), ohi = pt_lds_tr16(ofragt + 16 * PITCH + db * 32);
             const f16x8 ot8 = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
             dvt[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ot8, pf, dvt[db], 0, 0, 0);
-            const f16x4b qlo = ab_lds_tr16(qfragt + db * 32), qhi = ab_lds_tr16(qfragt + 16 * PITCH + db * 32);
+            const f16x4 qlo = pt_lds_tr16(qfragt + db * 32), qhi = pt_lds_tr16(qfragt + 16 * PITCH + db * 32);
             const f16x8 qt8 = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
             dkt[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qt8, dsf, dkt[db], 0, 0, 0);
         }
@@ -287,10 +280,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const f16* __restr
         f16* vp = dv + gk * lddk + hcol + 4 * g;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4b k4 = {(f16)(dkt[db][0] * scale), (f16)(dkt[db][1] * scale), (f16)(dkt[db][2] * scale), (f16)(dkt[db][3] * scale)};
-            const f16x4b v4 = {(f16)dvt[db][0], (f16)dvt[db][1], (f16)dvt[db][2], (f16)dvt[db][3]};
-            *(f16x4b*)(kp + db * 16) = k4;
-            *(f16x4b*)(vp + db * 16) = v4;
+            const f16x4 k4 = {(f16)(dkt[db][0] * scale), (f16)(dkt[db][1] * scale), (f16)(dkt[db][2] * scale), (f16)(dkt[db][3] * scale)};
+            const f16x4 v4 = {(f16)dvt[db][0], (f16)dvt[db][1], (f16)dvt[db][2], (f16)dvt[db][3]};
+            *(f16x4*)(kp + db * 16) = k4;
+            *(f16x4*)(vp + db * 16) = v4;
         }
     }
 }
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_kernel(const f16* __res
 #pragma unroll
         for (int i = 0; i < 4; ++i) dsb[i] = (f16)(e[i] * (db[i] - dd) * scale);
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                   // this wave's staged rows are in LDS
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                            // this wave's staged rows are in LDS
     __builtin_amdgcn_wave_barrier();
     f16* const gq = dqkv + row * ldd + head * HDIM + 4 * g;
 #pragma unroll

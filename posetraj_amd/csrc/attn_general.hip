@@ -18,14 +18,6 @@
 
 namespace {
 
-typedef f16 f16x4v __attribute__((ext_vector_type(4)));
-typedef __fp16 hw_f16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-__device__ __forceinline__ f16x4v ag_lds_tr16(const char* p) {
-    const hw_f16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hw_f16x4*)p);
-    return __builtin_bit_cast(f16x4v, v);
-}
-
 constexpr int AG_KT = 32;       // keys per tile
 constexpr int AG_QB = 64;       // queries per workgroup
 
@@ -149,8 +141,8 @@ __global__ __launch_bounds__(256, (D > 128 ? 1 : 2)) void attn_general_kernel(
         // ---- O^T += V^T P^T
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4v lo = ag_lds_tr16(vfrag + db * 32);
-            const f16x4v hi = ag_lds_tr16(vfrag + 16 * PITCH + db * 32);
+            const f16x4 lo = pt_lds_tr16(vfrag + db * 32);
+            const f16x4 hi = pt_lds_tr16(vfrag + 16 * PITCH + db * 32);
             const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             ot[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, ot[db], 0, 0, 0);
         }
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void attn_d512_kernel(
 
     const int nkt = (Sk + AG_KT - 1) / AG_KT;
     stage(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));
     __syncthreads();
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
@@ -283,12 +275,12 @@ __global__ __launch_bounds__(512, 2) void attn_d512_kernel(
         }
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            const f16x4v lo = ag_lds_tr16(Vs + voff + db * 32);
-            const f16x4v hi = ag_lds_tr16(Vs + voff + 16 * PITCH + db * 32);
+            const f16x4 lo = pt_lds_tr16(Vs + voff + db * 32);
+            const f16x4 hi = pt_lds_tr16(Vs + voff + 16 * PITCH + db * 32);
             const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             ot[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, ot[db], 0, 0, 0);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                    // this wave's copies of tile kt + 1 have landed
+        __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));             // this wave's copies of tile kt + 1 have landed
         __syncthreads();                                       // ... everyone's have, and everyone is done reading buffer buf
     }
     float l = l_run;

@@ -91,12 +91,10 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
 #pragma unroll
         for (int tt = 0; tt < 10; ++tt) Xf[r][tt] = *(const f16x8*)(xp + 32 * tt);
     }
-    const int swz = frow >> 1;
-    const int c0 = (fq ^ swz) * 16, c1 = ((fq + 4) ^ swz) * 16;                     // byte offsets of the two 32-deep k halves
-    const int csrc = (t & 7) ^ ((t >> 4) & 7);               // logical chunk a thread's copy stores (rows XOR-swizzled by (row >> 1) & 7)
+    const int c0 = lds_khalf_off(frow, fq, 0), c1 = lds_khalf_off(frow, fq, 1);     // byte offsets of the two 32-deep k halves
+    const int csrc = lds_src_chunk(t);                       // logical chunk a thread's copy stores
     const int lr = t >> 3;                                   // 0 .. 63
-    // W2 piece j of chunk c: LDS row (s, f, r) = (lr >> 5, (lr >> 4) & 1, lr & 15) holds W2 row 160 s + 32 j + 16 f + r
-    const int w2row0 = (lr >> 5) * 160 + ((lr >> 4) & 1) * 16 + (lr & 15);
+    const int w2row0 = lds_wpiece_row(lr);                   // W2 piece j of chunk c: LDS row lr holds W2 row w2row0 + 32 j
     // ---------------- LDS-DMA set-up.  One copy per thread moves 8 KiB: LDS row t >> 3, physical 16-B chunk t & 7
     // W1 K tile kt of chunk c: LDS rows 0 .. 127 = W1 rows 128 c + row (rows 0 .. 63 feed half s = 0, 64 .. 127 half s = 1)
     const int w1off = lr * fp.kpad1 + csrc * 8;              // + (128 c + 64 u) * kpad1 + 64 kt   (u = second copy)
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             for (int ni = 0; ni < TN; ++ni) { rs4[r][ni] = *(const f16x4*)(rp + ni * 16); vc4[r][ni] = *(const f16x4*)(vp + ni * vstep); }
         }
         stageWo(0, 0); stageWo(1, 1); stageWo(2, 2);
-        __builtin_amdgcn_s_waitcnt(0x0F7F);                  // vmcnt(15): the attention rows, bo, residual and row vector have landed, the 15 copies fly
+        __builtin_amdgcn_s_waitcnt(pt_vmcnt(15));            // the attention rows, bo, residual and row vector have landed, the 15 copies fly
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni)
 #pragma unroll
@@ -151,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
 #pragma unroll
         for (int kt = 0; kt < 5; ++kt) {
             // K tile kt has landed (this wave's copies): tiles kt + 1, kt + 2 (5 copies each) may still fly
-            if (kt < 3) __builtin_amdgcn_s_waitcnt(0x0F7A); else if (kt == 3) __builtin_amdgcn_s_waitcnt(0x0F75); else __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (kt < 3) __builtin_amdgcn_s_waitcnt(pt_vmcnt(10)); else if (kt == 3) __builtin_amdgcn_s_waitcnt(pt_vmcnt(5)); else __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));
             __builtin_amdgcn_s_barrier();
             if (kt == 4) { stageW1(0, 0); stageW1(1, 0); }   // buffer 0 (K tile 3) is read: the feed-forward's first two W1 tiles land under the LayerNorm
 #pragma unroll
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
                         acc2[ni][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wq[ni], Xf[r][2 * kt + kh], acc2[ni][r], 0, 0, 0);
             }
             if (kt + 3 < 5) {
-                __builtin_amdgcn_s_waitcnt(0xC07F);
+                __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
                 __builtin_amdgcn_s_barrier();                // every wave is done with buffer kt % 3
                 stageWo(kt + 3, kt % 3);
             }
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             sum += __shfl_xor(sum, 16); sum += __shfl_xor(sum, 32);
             if (fq == 0) part[(wr * 32 + r * 16 + frow) * 2 + wc] = sum;
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
             if (fq == 0) part[256 + rl * 2 + wc] = sq;
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_s_barrier();
         // ---- y = LayerNorm(h) -> fp16 -> the y tile (row pitch 656 B: the fragment reads below touch every bank once)
         const char* const gl = smem + F_LN_OFF + (wc * 160 + 4 * fq) * 2;
@@ -216,13 +214,13 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
                 *(f16x4*)(smem + F_Y_OFF + rl * F_YPITCH + (wc * 160 + ni * 16 + 4 * fq) * 2) = o;
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int tt = 0; tt < 10; ++tt) Xf[r][tt] = *(const f16x8*)(smem + F_Y_OFF + (wr * 32 + r * 16 + frow) * F_YPITCH + (32 * tt + 8 * fq) * 2);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_s_barrier();                        // the y tile is read: the weight ring may land on it
     }
     f16x4 b4[TN];
@@ -252,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
     for (int kt = PRE ? 2 : 0; kt < 5; ++kt) stageW1(kt, 0);
     stageW2(0, 0); stageW2(1, 0);
     if constexpr (PRE) {                                     // the residual of the feed-forward is h itself: the accumulators continue from h + b2
-        __builtin_amdgcn_s_waitcnt(0x0F78);                  // vmcnt(8): b2 (W1 tiles 2 .. 4 and the two W2 pieces stay in flight)
+        __builtin_amdgcn_s_waitcnt(pt_vmcnt(8));             // b2 (W1 tiles 2 .. 4 and the two W2 pieces stay in flight)
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni)
 #pragma unroll
@@ -262,15 +260,15 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
     } else {
         bias_init<CF, 12>(b4, acc2);                         // X, b2 (and the b1 copy) have landed; the 12 weight copies stay in flight
     }
-    __builtin_amdgcn_s_waitcnt(0x0F79);                      // vmcnt(9): K tile 0 (and 1) of W1
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(9));                 // K tile 0 (and 1) of W1
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
     __builtin_amdgcn_s_barrier();
     if constexpr (ST) ig_stamp(kp, wave, lane, 1);
 
     const char* const w1rd = smem + (wc * 64 + frow) * 128;                        // + kt * F_W1T + b * 2048
     const char* const w2rd = smem + F_W2_OFF + (wc * 32 + frow) * 128;             // + j * F_W2P + f * 2048
     const char* const hrd = smem + F_H_OFF + (wr * 32 + frow) * 128;               // + r * 2048
-    char* const hwr = smem + F_H_OFF + (wr * 32 + frow) * 128 + 8 * (fq & 1);      // + r * 2048 + ((4 s + 2 hb + (fq >> 1)) ^ swz) * 16
+    char* const hwr = smem + F_H_OFF + (wr * 32 + frow) * 128 + 8 * (fq & 1);      // + r * 2048 + lds_chunk_off(frow, 4 s + 2 hb + (fq >> 1))
     const char* const b1rd = smem + F_B1_OFF + (wc * 64 + 4 * fq) * 2;             // + (128 c + 16 b) * 2
     f32x4 acc1[4][2];
     f16x8 Wf[4][2], Hf[2][2];
@@ -278,11 +276,11 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
 #define FF_PHASE_MMA(body0, body1)                                                             \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     __builtin_amdgcn_s_barrier();                                                              \
-    __builtin_amdgcn_s_waitcnt(0xC47F);                      /* lgkmcnt(4): the first k halves */ \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(4));               /* the first k halves */ \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     body0                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                         \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                        \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     body1                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -303,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
     _Pragma("unroll") for (int r_ = 0; r_ < 2; ++r_)                                            \
         _Pragma("unroll") for (int b_ = 0; b_ < (nb); ++b_)                                     \
             acc2[2 * (j0) + b_][r_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wf[b_][h_], Hf[r_][h_], acc2[2 * (j0) + b_][r_], 0, 0, 0);
-#define FF_VMWAIT __builtin_amdgcn_s_waitcnt(0x0F79);        /* vmcnt(9): everything issued five phases ago has landed */
+#define FF_VMWAIT __builtin_amdgcn_s_waitcnt(pt_vmcnt(9));   /* everything issued five phases ago has landed */
 
     const bool late = wave >= 4;
     if (late) __builtin_amdgcn_s_barrier();
@@ -317,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             for (int b = 0; b < 4; ++b) bb[b] = *(const f16x4*)(b1rd + (128 * c + 16 * b) * 2);
             FF_READ_W1(0)
             stageW2(2, c); stageW2(3, c);
-            __builtin_amdgcn_s_waitcnt(0xC87F);              // lgkmcnt(8): the four bias reads
+            __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(8));       // the four bias reads
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const f32x4 v = {(float)bb[b][0], (float)bb[b][1], (float)bb[b][2], (float)bb[b][3]};
@@ -329,11 +327,11 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         FF_ST(9)
-        __builtin_amdgcn_s_waitcnt(0xC47F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(4));
         __builtin_amdgcn_sched_barrier(0);
         FF_MMA1(0, 0)
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_sched_barrier(0);
         FF_MMA1(0, 1)
         __builtin_amdgcn_sched_barrier(0);
@@ -375,14 +373,14 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
                     float p0 = val[0] * g01[0], p1 = val[1] * g01[1], p2 = val[2] * g23[0], p3 = val[3] * g23[1];
                     asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
                     const f16x4 o = {(f16)p0, (f16)p1, (f16)p2, (f16)p3};
-                    *(f16x4*)(hwr + r * 2048 + ((4 * wc + 2 * hb + (fq >> 1)) ^ swz) * 16) = o;
+                    *(f16x4*)(hwr + r * 2048 + lds_chunk_off(frow, 4 * wc + 2 * hb + (fq >> 1))) = o;
                 }
             __builtin_amdgcn_sched_barrier(0);
             FF_READ_W2(0)
             stageW1(3, c + 1);
             FF_VMWAIT
             __builtin_amdgcn_sched_barrier(0);               // the count below is only right with all 8 W2 reads ISSUED in front of it
-            __builtin_amdgcn_s_waitcnt(0xC87F);              // lgkmcnt(8): this wave's h stores are in LDS (the W2 reads may still fly)
+            __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(8));       // this wave's h stores are in LDS (the W2 reads may still fly)
             FF_ST(12)
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -391,11 +389,11 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             for (int h_ = 0; h_ < 2; ++h_)
 #pragma unroll
                 for (int r = 0; r < 2; ++r) Hf[r][h_] = *(const f16x8*)(hrd + r * 2048 + (h_ ? c1 : c0));
-            __builtin_amdgcn_s_waitcnt(0xC27F);              // lgkmcnt(2): W2 fragments and the first k half of h
+            __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(2));       // W2 fragments and the first k half of h
             __builtin_amdgcn_sched_barrier(0);
             FF_MMA2(0, 4, 0)
             __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
             __builtin_amdgcn_sched_barrier(0);
             FF_MMA2(0, 4, 1)
             __builtin_amdgcn_sched_barrier(0);
@@ -417,11 +415,11 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
         FF_VMWAIT
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_waitcnt(0xC27F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(2));
         __builtin_amdgcn_sched_barrier(0);
         FF_MMA2(4, 2, 0)
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
         __builtin_amdgcn_sched_barrier(0);
         FF_MMA2(4, 2, 1)
         __builtin_amdgcn_sched_barrier(0);
@@ -441,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
         igemm_epilogue<CF, VAR>(kp, acc2, smem, m0, 0, wave, lane_t);
     }
 #undef FF_ST
-    __builtin_amdgcn_s_waitcnt(0x0F70);                      // no LDS-DMA may outlive the wave
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
 }
 
 typedef void (*ffn_kernel_t)(const FParams);

@@ -23,13 +23,6 @@ constexpr int GK = 64, GPITCH = GK + 8;          // K step; [row][k] rows: 64 + 
 constexpr int TRPAD = 16;                        // [k][row] rows: ROWS + 16 halfs - the 8 k-rows a 32-lane half of ds_read_b64_tr_b16
                                                  // touches start 8 banks apart (pitch / 2 = 8 mod 64 dwords for ROWS = 32 ... 256)
 
-typedef _Float16 g_f16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 g_hw_f16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-__device__ __forceinline__ g_f16x4 g_lds_tr16(const f16* p) {
-    const g_hw_f16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) g_hw_f16x4*)p);
-    return __builtin_bit_cast(g_f16x4, v);
-}
-
 __device__ __attribute__((aligned(16))) unsigned g_gemm_zeros[4];      // 16 zero bytes: the source of every out-of-range group
 
 struct Operand {
@@ -144,15 +137,15 @@ __device__ __forceinline__ void store_group(f16* lds, bool kcontig, int grp, f16
 template <int ROWS>
 __device__ __forceinline__ f16x8 fragment(const f16* lds, bool kcontig, int rbase, int lane, int kk) {
     const int c = lane & 15, g = lane >> 4;
-    g_f16x4 lo, hi;
+    f16x4 lo, hi;
     if (kcontig) {
         const f16* p = lds + (rbase + c) * GPITCH + 32 * kk + 4 * g;
-        lo = *(const g_f16x4*)p;
-        hi = *(const g_f16x4*)(p + 16);
+        lo = *(const f16x4*)p;
+        hi = *(const f16x4*)(p + 16);
     } else {
         const f16* p = lds + (32 * kk + 4 * g + (c >> 2)) * (ROWS + TRPAD) + rbase + 4 * (c & 3);
-        lo = g_lds_tr16(p);
-        hi = g_lds_tr16(p + 16 * (ROWS + TRPAD));
+        lo = pt_lds_tr16(p);
+        hi = pt_lds_tr16(p + 16 * (ROWS + TRPAD));
     }
     return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }

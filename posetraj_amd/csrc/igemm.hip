@@ -25,46 +25,115 @@
 
 namespace {
 
+// ---------------------------------------------------------------- the im2col gather and the tile order, shared by the three kernels
+// Tile order: XCD-contiguous chunks (pt_xcd_remap, done by the caller), and inside them "grouped" rasterisation - kp.gm consecutive
+// M tiles share one N tile (one weight panel) before the next N tile starts, so the ~32 workgroups an XCD runs at
+// once form a gm x (32 / gm) block of the tile grid and both operand panels are shared through its L2.  The plain
+// N-fastest order re-streamed the whole weight matrix from beyond L2 once per M-tile row (FETCH_SIZE: 26x the
+// algorithmic bytes on the 16128 x 10240 x 1280 GEGLU projection).
+__device__ __forceinline__ void tile_of(const KParams& kp, int bid, int& tile_m, int& tile_n) {
+    const int gsz = kp.gm * kp.tiles_n, grp = bid / gsz, first_m = grp * kp.gm;
+    const int gm = min(kp.gm, kp.tiles_m - first_m), within = bid - grp * gsz;
+    tile_m = first_m + within % gm; tile_n = within / gm;
+}
+
+// Output row m -> iyx = (iy0 << 16 | ix0 & 0xffff), the top-left tap of its pixel, and pix0, the pixel base of its image.
+// One-column kernels (kp.foldx) fold the output column into pix0 and keep ix0 = 0.
+__device__ __forceinline__ void row_origin(const KParams& kp, int m, int& iyx, int& pix0) {
+    const pt_igemm_params& p = kp.p;
+    if (m < p.M) {
+        const int HWo = p.Hout * p.Wout;
+        int img = m, oy = 0, ox = 0;                         // linear layers (one-pixel images) skip the two divisions
+        if (HWo != 1) {
+            img = m / HWo;
+            const int rem = m - img * HWo;
+            oy = rem / p.Wout; ox = rem - oy * p.Wout;
+        }
+        iyx = ((oy * p.stride - p.pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - p.pad_w) & 0xffff);
+        pix0 = img * p.Hin * p.Win + (kp.foldx ? ox : 0);
+    } else {
+        iyx = (int)0xC0000000; pix0 = 0;                     // iy0 = -16384: every tap is out of bounds
+    }
+}
+
+// Where tap (ky, kx) of a decoded row reads channel `cofs` of `src` (pitch ld): bounds test in the (upsampled) input extent,
+// nearest-2x upsampling as a coordinate shift, and the zero page `zsrc` for padded taps (ok = false).
+__device__ __forceinline__ const f16* tap_source(const pt_igemm_params& p, int iyx, int pix0, int ky, int kx, const f16* src, int ld,
+                                                 int cofs, const f16* zsrc, int Hlim, int Wlim, bool& ok) {
+    int iy = (iyx >> 16) + ky, ix = (int)(short)(iyx & 0xffff) + kx;
+    ok = ok && (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
+    if (p.upsample2x) { iy >>= 1; ix >>= 1; }
+    return ok ? src + ((size_t)(pix0 + iy * p.Win + ix) * ld + cofs) : zsrc;
+}
+
+// Channel-aligned K tiles (every 64-wide K tile lies inside one tap of one source): the gather is kept as one source pointer per
+// slot, recomputed here only when the tap or the source changes and otherwise just advanced by the channel offset - the full
+// address arithmetic per copy (~25 VALU) was costing as many issue cycles as the MFMAs.  Bit i of avalid: slot i reads real data.
+// The scalars come by reference, like the lambda captures this function replaced: taken by value, the same arithmetic was
+// register-allocated differently in the pipelined kernels (up to 12 more SGPR spills in igemm10_kernel; by reference: none).
+template <int SLOTS>
+__device__ __forceinline__ void retarget(const pt_igemm_params& p, const int (&iyx)[SLOTS], const int (&pix0)[SLOTS], const int& tap, const int& source,
+                                         const int& csrc, const f16* const& zsrc, const int& Hlim, const int& Wlim, const f16* (&aptr)[SLOTS], unsigned& avalid) {
+    const int ky = tap / p.KW, kx = tap - ky * p.KW;
+    const f16* src = source ? (const f16*)p.x1 : (const f16*)p.x0;
+    const int ld = source ? p.ld1 : p.ld0;
+    avalid = 0;
+#pragma unroll
+    for (int i = 0; i < SLOTS; ++i) {
+        bool ok = true;
+        aptr[i] = tap_source(p, iyx[i], pix0[i], ky, kx, src, ld, csrc * 8, zsrc, Hlim, Wlim, ok);
+        avalid |= ok ? (1u << i) : 0u;
+    }
+}
+
+// One K tile further in the (tap, source, channel) walk.
+__device__ __forceinline__ void walk_step(const pt_igemm_params& p, int& s_tap, int& s_src, int& s_ci) {
+    s_ci += BK;
+    if (s_ci == (s_src ? p.C1 : p.C0)) {
+        s_ci = 0;
+        if (s_src == 0 && p.C1 > 0) s_src = 1;
+        else { s_src = 0; ++s_tap; }
+    }
+}
+
+// Past the last K tile the X copies of the pipelined kernels carry no operand data: aim them at this wave's block of the residual
+// (first dummy tile) and of the blend input (second), one 128-byte line per lane, so the epilogue's side
+// loads - issued ~2 K tiles later - hit L2 instead of paying an HBM round trip per row pass.
+template <int TN>
+__device__ __forceinline__ void side_targets(const pt_igemm_params& p, bool first, int m0, int n0, int wave, int lane, const f16* zsrc,
+                                             const f16* (&aptr)[4]) {
+    const f16* side = first ? (const f16*)p.res : (const f16*)p.blend;
+    const int ldside = first ? p.ldr : p.ldb;
+    const int nw = p.act == 1 ? TN * 8 : TN * 16;                              // this wave's output columns
+    const int wcol = p.act == 1 ? (n0 + (wave & 1) * TN * 16) / 2 : n0 + (wave & 1) * TN * 16;
+    const int nout = p.act == 1 ? p.N / 2 : p.N;
+    const int mrow = min(m0 + (wave >> 1) * 64 + lane, p.M - 1);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int c = wcol + min(a * 64, nw - 8);
+        aptr[a] = (side && c + 8 <= nout) ? side + ((size_t)mrow * ldside + c) : zsrc;
+    }
+}
+
 template <class CF, bool FAST>
 __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TM = CF::TM, TN = CF::TN, NT = CF::NT, BM = CF::BM, BN = CF::BN;
     const pt_igemm_params& p = kp.p;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // Tile order: XCD-contiguous chunks (pt_xcd_remap), and inside them "grouped" rasterisation - kp.gm consecutive
-    // M tiles share one N tile (one weight panel) before the next N tile starts, so the ~32 workgroups an XCD runs at
-    // once form a gm x (32 / gm) block of the tile grid and both operand panels are shared through its L2.  The plain
-    // N-fastest order re-streamed the whole weight matrix from beyond L2 once per M-tile row (FETCH_SIZE: 26x the
-    // algorithmic bytes on the 16128 x 10240 x 1280 GEGLU projection).
     const int bid = pt_xcd_remap(blockIdx.x, gridDim.x);
-    const int gsz = kp.gm * kp.tiles_n, grp = bid / gsz, first_m = grp * kp.gm;
-    const int gm = min(kp.gm, kp.tiles_m - first_m), within = bid - grp * gsz;
-    const int tile_m = first_m + within % gm, tile_n = within / gm;
+    int tile_m, tile_n;
+    tile_of(kp, bid, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
 
     // ---------------- staging set-up: this thread copies chunk slot (t + NT i) of each tile
-    const int csrc = (t & 7) ^ ((t >> 4) & 7);               // source chunk (row parity bits are i-independent)
+    const int csrc = lds_src_chunk(t);                       // (row parity bits are i-independent)
     const int Ctot = p.C0 + p.C1;
-    const int HWo = p.Hout * p.Wout;
-    int iyx[CF::A_SLOTS], pix0[CF::A_SLOTS];                  // (iy0 << 16 | ix0 & 0xffff): top-left tap of the output pixel
+    int iyx[CF::A_SLOTS], pix0[CF::A_SLOTS];
 #pragma unroll
-    for (int i = 0; i < CF::A_SLOTS; ++i) {
-        const int m = m0 + (t >> 3) + (NT / 8) * i;
-        if (m < p.M) {
-            int img = m, oy = 0, ox = 0;                     // linear layers (one-pixel images) skip the two divisions
-            if (HWo != 1) {
-                img = m / HWo;
-                const int rem = m - img * HWo;
-                oy = rem / p.Wout; ox = rem - oy * p.Wout;
-            }
-            iyx[i] = ((oy * p.stride - p.pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - p.pad_w) & 0xffff);
-            pix0[i] = img * p.Hin * p.Win + (kp.foldx ? ox : 0);
-        } else {
-            iyx[i] = (int)0xC0000000; pix0[i] = 0;            // iy0 = -16384: every tap is out of bounds
-        }
-    }
+    for (int i = 0; i < CF::A_SLOTS; ++i) row_origin(kp, m0 + (t >> 3) + (NT / 8) * i, iyx[i], pix0[i]);
     const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
     int woff[CF::B_SLOTS];
@@ -77,41 +146,19 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     const f16* wbase = (const f16*)p.w;
     const int nk = p.Kpad / BK;
 
-    // FAST path (every 64-wide K tile lies inside one tap of one source): the im2col gather is kept as one source
-    // pointer per slot, recomputed only when the tap or the source changes and otherwise just advanced by the channel
-    // offset - the full address arithmetic per copy (~25 VALU) was costing as many issue cycles as the MFMAs.
-    const f16* aptr[CF::A_SLOTS];
+    const f16* aptr[CF::A_SLOTS];                            // FAST path: channel-aligned K tiles (retarget)
     unsigned avalid = 0;
     int s_tap = 0, s_src = 0, s_ci = 0;                      // wave-uniform position of the next tile to stage
-    auto retarget = [&]() {
-        const int ky = s_tap / p.KW, kx = s_tap - ky * p.KW;
-        const f16* src = s_src ? (const f16*)p.x1 : (const f16*)p.x0;
-        const int ld = s_src ? p.ld1 : p.ld0;
-        avalid = 0;
-#pragma unroll
-        for (int i = 0; i < CF::A_SLOTS; ++i) {
-            int iy = (iyx[i] >> 16) + ky, ix = (int)(short)(iyx[i] & 0xffff) + kx;
-            const bool ok = (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
-            if (p.upsample2x) { iy >>= 1; ix >>= 1; }
-            aptr[i] = ok ? src + ((size_t)(pix0[i] + iy * p.Win + ix) * ld + csrc * 8) : zsrc;
-            avalid |= ok ? (1u << i) : 0u;
-        }
-    };
 
     auto stage = [&](int kt, int buf) {
         char* As = smem + buf * CF::STAGE;
         char* Bs = As + CF::A_BYTES;
         if (FAST) {
-            if (s_ci == 0) retarget();
+            if (s_ci == 0) retarget(p, iyx, pix0, s_tap, s_src, csrc, zsrc, Hlim, Wlim, aptr, avalid);
 #pragma unroll
             for (int i = 0; i < CF::A_SLOTS; ++i)
                 pt_glds16(aptr[i] + (((avalid >> i) & 1u) ? s_ci : 0), As + (wave * 64 + NT * i) * 16);
-            s_ci += BK;
-            if (s_ci == (s_src ? p.C1 : p.C0)) {
-                s_ci = 0;
-                if (s_src == 0 && p.C1 > 0) s_src = 1;
-                else { s_src = 0; ++s_tap; }
-            }
+            walk_step(p, s_tap, s_src, s_ci);
         } else {
             const int kg = kt * BK + csrc * 8;
             const bool kvalid = kg < p.K;
@@ -122,11 +169,8 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
             else           { src = (const f16*)p.x1; ld = p.ld1; cofs = ci - p.C0; }
 #pragma unroll
             for (int i = 0; i < CF::A_SLOTS; ++i) {
-                int iy = (iyx[i] >> 16) + ky, ix = (int)(short)(iyx[i] & 0xffff) + kx;
-                const bool ok = kvalid && (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
-                if (p.upsample2x) { iy >>= 1; ix >>= 1; }
-                const f16* g = ok ? src + ((size_t)(pix0[i] + iy * p.Win + ix) * ld + cofs) : zsrc;
-                pt_glds16(g, As + (wave * 64 + NT * i) * 16);
+                bool ok = kvalid;
+                pt_glds16(tap_source(p, iyx[i], pix0[i], ky, kx, src, ld, cofs, zsrc, Hlim, Wlim, ok), As + (wave * 64 + NT * i) * 16);
             }
         }
 #pragma unroll
@@ -137,7 +181,6 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     // ---------------- MFMA set-up
     const int wr = wave / CF::WN, wc = wave % CF::WN;
     const int frow = lane & 15, fq = lane >> 4;
-    const int swz = frow >> 1;                               // (row >> 1) & 7 for every fragment row of this lane
     f32x4 acc[TN][TM];
 
     // Tiles with register headroom (DB) issue the ds_reads of BOTH 32-deep fragment sets before the first MFMA (the
@@ -151,7 +194,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
             f16x8 xf[2][TM], wf[2][TN];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int coff = ((fq + 4 * ks) ^ swz) * 16;
+                const int coff = lds_khalf_off(frow, fq, ks);
 #pragma unroll
                 for (int i = 0; i < TM; ++i) xf[ks][i] = *(const f16x8*)(As + i * 2048 + coff);
 #pragma unroll
@@ -170,7 +213,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
         } else {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int coff = ((fq + 4 * ks) ^ swz) * 16;
+                const int coff = lds_khalf_off(frow, fq, ks);
                 f16x8 xf[TM];
 #pragma unroll
                 for (int i = 0; i < TM; ++i) xf[i] = *(const f16x8*)(As + i * 2048 + coff);
@@ -231,34 +274,20 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
     const pt_igemm_params& p = kp.p;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int bid = pt_xcd_remap(blockIdx.x, gridDim.x);
-    const int gsz = kp.gm * kp.tiles_n, grp = bid / gsz, first_m = grp * kp.gm;
-    const int gm = min(kp.gm, kp.tiles_m - first_m), within = bid - grp * gsz;
-    const int tile_m = first_m + within % gm, tile_n = within / gm;
+    int tile_m, tile_n;
+    tile_of(kp, bid, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
     ig_stamp(kp, wave, lane, 0);
 
     // ---------------- staging set-up.  Slot a = 2 h + s: piece h, copy s of this thread (chunk t + 512 s of the piece)
-    const int csrc = (t & 7) ^ ((t >> 4) & 7);
-    const int HWo = p.Hout * p.Wout;
+    const int csrc = lds_src_chunk(t);
     int iyx[4], pix0[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int h = a >> 1, sl = a & 1;
-        const int m = m0 + ((t >> 8) + 2 * sl) * 64 + h * 32 + ((t >> 3) & 31);
-        if (m < p.M) {
-            int img = m, oy = 0, ox = 0;                     // linear layers (one-pixel images) skip the two divisions
-            if (HWo != 1) {
-                img = m / HWo;
-                const int rem = m - img * HWo;
-                oy = rem / p.Wout; ox = rem - oy * p.Wout;
-            }
-            iyx[a] = ((oy * p.stride - p.pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - p.pad_w) & 0xffff);
-            pix0[a] = img * p.Hin * p.Win + (kp.foldx ? ox : 0);
-        } else {
-            iyx[a] = (int)0xC0000000; pix0[a] = 0;
-        }
+        row_origin(kp, m0 + ((t >> 8) + 2 * sl) * 64 + h * 32 + ((t >> 3) & 31), iyx[a], pix0[a]);
     }
     const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
@@ -278,43 +307,12 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
     bool a_past = false;                                     // the X pieces being staged lie past the last K tile
     auto advanceA = [&]() {                                  // fix the source pointers of K tile st_tile (both X pieces)
         if (st_tile >= nk) {
-            // Past the last K tile the X copies carry no operand data: aim them at this wave's block of the residual
-            // (first dummy tile) and of the blend input (second), one 128-byte line per lane, so the epilogue's side
-            // loads - issued ~2 K tiles later - hit L2 instead of paying an HBM round trip per row pass.
-            const f16* side = st_tile == nk ? (const f16*)p.res : (const f16*)p.blend;
-            const int ldside = st_tile == nk ? p.ldr : p.ldb;
-            const int nw = p.act == 1 ? TN * 8 : TN * 16;                              // this wave's output columns
-            const int wcol = p.act == 1 ? (n0 + (wave & 1) * TN * 16) / 2 : n0 + (wave & 1) * TN * 16;
-            const int nout = p.act == 1 ? p.N / 2 : p.N;
-            const int mrow = min(m0 + (wave >> 1) * 64 + lane, p.M - 1);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const int c = wcol + min(a * 64, nw - 8);
-                aptr[a] = (side && c + 8 <= nout) ? side + ((size_t)mrow * ldside + c) : zsrc;
-            }
+            side_targets<TN>(p, st_tile == nk, m0, n0, wave, lane, zsrc, aptr);   // the epilogue's side inputs into L2
             avalid = 0; ci_cur = 0; a_past = true;
         } else {
-            if (s_ci == 0) {
-                const int ky = s_tap / p.KW, kx = s_tap - ky * p.KW;
-                const f16* src = s_src ? (const f16*)p.x1 : (const f16*)p.x0;
-                const int ld = s_src ? p.ld1 : p.ld0;
-                avalid = 0;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    int iy = (iyx[a] >> 16) + ky, ix = (int)(short)(iyx[a] & 0xffff) + kx;
-                    const bool ok = (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
-                    if (p.upsample2x) { iy >>= 1; ix >>= 1; }
-                    aptr[a] = ok ? src + ((size_t)(pix0[a] + iy * p.Win + ix) * ld + csrc * 8) : zsrc;
-                    avalid |= ok ? (1u << a) : 0u;
-                }
-            }
+            if (s_ci == 0) retarget(p, iyx, pix0, s_tap, s_src, csrc, zsrc, Hlim, Wlim, aptr, avalid);
             ci_cur = s_ci;
-            s_ci += BK;
-            if (s_ci == (s_src ? p.C1 : p.C0)) {
-                s_ci = 0;
-                if (s_src == 0 && p.C1 > 0) s_src = 1;
-                else { s_src = 0; ++s_tap; }
-            }
+            walk_step(p, s_tap, s_src, s_ci);
         }
         ++st_tile;
     };
@@ -337,8 +335,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
     // ---------------- MFMA set-up
     const int wr = wave >> 1, wc = wave & 1;
     const int frow = lane & 15, fq = lane >> 4;
-    const int swz = frow >> 1;
-    const int c0 = (fq ^ swz) * 16, c1 = ((fq + 4) ^ swz) * 16;            // byte offsets of the two 32-deep k halves
+    const int c0 = lds_khalf_off(frow, fq, 0), c1 = lds_khalf_off(frow, fq, 1);
     const char* const xrd = smem + (wr * 32 + frow) * 128;
     const char* const wrd = smem + 2 * PIECE + (wc * 64 + frow) * 128;
     f32x4 acc[TN][TM];
@@ -359,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
                 acc[(hw) * 4 + n_][(hx) * 2 + m_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(    \
                     Wf[n_][ks_], Xv[m_][ks_], acc[(hw) * 4 + n_][(hx) * 2 + m_], 0, 0, 0);
 #define IG8_MMA(Xv, hx, hw)                                                                    \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                        \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     IG8_MMA_HALF(Xv, hx, hw, 0)                                                                \
     IG8_MMA_HALF(Xv, hx, hw, 1)                                                                \
@@ -369,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
     advanceA(); stageX(0, 0); stageW(0, 0, 0); stageX(1, 0); stageW(1, 0, 0);
     advanceA(); stageX(0, BUF); stageW(0, BUF, 1); stageX(1, BUF);
     bias_init<CF, 14>(b4, acc);
-    __builtin_amdgcn_s_waitcnt(0x0F76);                      // vmcnt(6)
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(6));
     __builtin_amdgcn_s_barrier();
     ig_stamp(kp, wave, lane, 1);
     const bool late = wave >= 4;                             // the group that runs one barrier behind
@@ -383,7 +380,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         IG8_READW(0, bo)
         stageW(1, bo1, kt + 1);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xC87F);                  // lgkmcnt(8): the X0 reads are done before anyone restages X0
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(8));          // the X0 reads are done before anyone restages X0
         __builtin_amdgcn_s_barrier();
         IG8_MMA(X0, 0, 0)
         __builtin_amdgcn_s_barrier();
@@ -405,7 +402,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         // ---- phase 4
         stageX(1, bo);
         __builtin_amdgcn_sched_barrier(0);
-        if (kt + 1 < nk) __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6): K tile kt+1 has landed (this wave's copies)
+        if (kt + 1 < nk) __builtin_amdgcn_s_waitcnt(pt_vmcnt(6));   // K tile kt+1 has landed (this wave's copies)
         __builtin_amdgcn_s_barrier();
         IG8_MMA(X0, 0, 1)
         __builtin_amdgcn_s_barrier();
@@ -424,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         igemm_epilogue<CF, VAR>(kp, acc, smem, m0, n0, wave, lane_t);
     }
     ig_stamp(kp, wave, lane, 3);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                      // no LDS-DMA may outlive the wave
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
 }
 
 // ============================================================================ 256 x 320, 10-phase ping-pong main loop
@@ -455,39 +452,22 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     const int ntiles = kp.tiles_m * kp.tiles_n;
     const int bid_all = pt_xcd_remap(blockIdx.x, gridDim.x);
     const int split = bid_all / ntiles, bid = bid_all - split * ntiles;
-    const int gsz = kp.gm * kp.tiles_n, grp = bid / gsz, first_m = grp * kp.gm;
-    const int gm = min(kp.gm, kp.tiles_m - first_m), within = bid - grp * gsz;
-    const int tile_m = first_m + within % gm, tile_n = within / gm;
+    int tile_m, tile_n;
+    tile_of(kp, bid, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
     ig_stamp(kp, wave, lane, 0);
 
     // ---------------- staging set-up.  X slot a = 2 h + s: pixel row a*64 + (t >> 3); W piece j: one copy per thread
-    const int csrc = (t & 7) ^ ((t >> 4) & 7);
-    const int HWo = p.Hout * p.Wout;
+    const int csrc = lds_src_chunk(t);
     int iyx[4], pix0[4];
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int m = m0 + a * 64 + (t >> 3);
-        if (m < p.M) {
-            int img = m, oy = 0, ox = 0;                     // linear layers (one-pixel images) skip the two divisions
-            if (HWo != 1) {
-                img = m / HWo;
-                const int rem = m - img * HWo;
-                oy = rem / p.Wout; ox = rem - oy * p.Wout;
-            }
-            iyx[a] = ((oy * p.stride - p.pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - p.pad_w) & 0xffff);
-            pix0[a] = img * p.Hin * p.Win + (kp.foldx ? ox : 0);
-        } else {
-            iyx[a] = (int)0xC0000000; pix0[a] = 0;
-        }
-    }
+    for (int a = 0; a < 4; ++a) row_origin(kp, m0 + a * 64 + (t >> 3), iyx[a], pix0[a]);
     const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
     // weight row of this thread's chunk in piece j: n0 + wc*160 + (2j + f)*16 + r with (wc, f, r) from LDS row t >> 3
-    const int wlr = t >> 3;
-    const int wrow0 = n0 + (wlr >> 5) * 160 + ((wlr >> 4) & 1) * 16 + (wlr & 15);
+    const int wrow0 = n0 + lds_wpiece_row(t >> 3);
     int woff[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -514,44 +494,15 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     }
     auto advanceA = [&]() {
         if (st_tile >= nk) {
-            // Past the last K tile the X copies carry no operand data: aim them at this wave's block of the residual
-            // (first dummy tile) and of the blend input (second), one 128-byte line per lane, so the epilogue's side
-            // loads - issued ~2 K tiles later - hit L2 instead of paying an HBM round trip per row pass.
-            const f16* side = st_tile == nk ? (const f16*)p.res : (const f16*)p.blend;
-            const int ldside = st_tile == nk ? p.ldr : p.ldb;
-            const int nw = p.act == 1 ? TN * 8 : TN * 16;                              // this wave's output columns
-            const int wcol = p.act == 1 ? (n0 + (wave & 1) * TN * 16) / 2 : n0 + (wave & 1) * TN * 16;
-            const int nout = p.act == 1 ? p.N / 2 : p.N;
-            const int mrow = min(m0 + (wave >> 1) * 64 + lane, p.M - 1);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const int c = wcol + min(a * 64, nw - 8);
-                aptr[a] = (side && c + 8 <= nout) ? side + ((size_t)mrow * ldside + c) : zsrc;
-            }
+            side_targets<TN>(p, st_tile == nk, m0, n0, wave, lane, zsrc, aptr);   // the epilogue's side inputs into L2
             avalid = 0; ci_cur = 0; a_past = true;
         } else {
             if (s_ci == 0 || a_fresh) {
                 a_fresh = false;
-                const int ky = s_tap / p.KW, kx = s_tap - ky * p.KW;
-                const f16* src = s_src ? (const f16*)p.x1 : (const f16*)p.x0;
-                const int ld = s_src ? p.ld1 : p.ld0;
-                avalid = 0;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    int iy = (iyx[a] >> 16) + ky, ix = (int)(short)(iyx[a] & 0xffff) + kx;
-                    const bool ok = (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
-                    if (p.upsample2x) { iy >>= 1; ix >>= 1; }
-                    aptr[a] = ok ? src + ((size_t)(pix0[a] + iy * p.Win + ix) * ld + csrc * 8) : zsrc;
-                    avalid |= ok ? (1u << a) : 0u;
-                }
+                retarget(p, iyx, pix0, s_tap, s_src, csrc, zsrc, Hlim, Wlim, aptr, avalid);
             }
             ci_cur = s_ci;
-            s_ci += BK;
-            if (s_ci == (s_src ? p.C1 : p.C0)) {
-                s_ci = 0;
-                if (s_src == 0 && p.C1 > 0) s_src = 1;
-                else { s_src = 0; ++s_tap; }
-            }
+            walk_step(p, s_tap, s_src, s_ci);
         }
         ++st_tile;
     };
@@ -572,8 +523,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     // ---------------- MFMA set-up
     const int wr = wave >> 1, wc = wave & 1;
     const int frow = lane & 15, fq = lane >> 4;
-    const int swz = frow >> 1;
-    const int c0 = (fq ^ swz) * 16, c1 = ((fq + 4) ^ swz) * 16;
+    const int c0 = lds_khalf_off(frow, fq, 0), c1 = lds_khalf_off(frow, fq, 1);
     const char* const xrd = smem + (wr * 64 + frow) * 128;
     const char* const wrd = smem + 2 * XP + (wc * 32 + frow) * 128;
     f32x4 acc[TN][TM];
@@ -595,11 +545,11 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
 #define IG10_PHASE_END(j)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     __builtin_amdgcn_s_barrier();                                                              \
-    __builtin_amdgcn_s_waitcnt((j) == 0 ? 0xC67F : 0xC27F);   /* lgkmcnt(6 | 2): the first k halves */ \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt((j) == 0 ? 6 : 2));   /* the first k halves */       \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     IG10_MMA_HALF(j, 0)                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                         \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                        \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     IG10_MMA_HALF(j, 1)                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -611,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     for (int j = 0; j < 5; ++j) stageW(j, 0, 0);
     advanceA(); stageX(0, BUF); stageX(1, BUF); stageW(0, BUF, 1); stageW(1, BUF, 1); stageW(2, BUF, 1);
     bias_init<CF, 16>(b4, acc);
-    __builtin_amdgcn_s_waitcnt(0x0F77);                      // vmcnt(7)
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(7));
     __builtin_amdgcn_s_barrier();
     ig_stamp(kp, wave, lane, 1);
     const bool late = wave >= 4;
@@ -648,7 +598,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
         stageW(1, bo, kt + 2);
         stageW(2, bo, kt + 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (kt + 1 < nk) __builtin_amdgcn_s_waitcnt(0x0F77);  // vmcnt(7): K tile kt+1 has landed (this wave's copies)
+        if (kt + 1 < nk) __builtin_amdgcn_s_waitcnt(pt_vmcnt(7));   // K tile kt+1 has landed (this wave's copies)
         IG10_PHASE_END(4)
     }
     if (!late) __builtin_amdgcn_s_barrier();
@@ -670,13 +620,13 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
                 if (m < p.M && n < p.N) *(f32x4*)(wsp + (size_t)m * p.N + n) = acc[ni][mi];
             }
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));
     } else {
         int lane_t = lane;                                   // (opaque: keeps the tail's lane-derived values below the K loop)
         asm volatile("" : "+v"(lane_t));
         igemm_epilogue<CF, VAR>(kp, acc, smem, m0, n0, wave, lane_t);
         ig_stamp(kp, wave, lane, 3);
-        __builtin_amdgcn_s_waitcnt(0x0F70);                  // no LDS-DMA may outlive the wave
+        __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));             // no LDS-DMA may outlive the wave
     }
 }
 
@@ -832,33 +782,26 @@ void launch(const KParams& kp, bool fast, hipStream_t s) {
     else      launch<CF, false>(kp, s);
 }
 
+// The pipelined kernels, one instance per tail variant (split-K - kp.ws set - exists on the 256 x 320 tile only).  LDS: the
+// tile's ring + the trash rows.
 typedef void (*pipe_kernel_t)(const KParams);
-
-void launch8(const KParams& kp, hipStream_t s) {
-    static const pipe_kernel_t table[V_COUNT] = {igemm8_kernel<V_P0>, igemm8_kernel<V_P1>, igemm8_kernel<V_P2>, igemm8_kernel<V_EW>,
-                                                 igemm8_kernel<V_W0>, igemm8_kernel<V_W1>, igemm8_kernel<V_W2>, igemm8_kernel<V_G0>,
-                                                 igemm8_kernel<V_GEW>, nullptr};
-    static bool attr_done[64][V_COUNT] = {};
-    const int dev = pt_device(), var = tail_variant(kp.p);
-    if (!attr_done[dev][var]) {
-        (void)hipFuncSetAttribute((const void*)table[var], hipFuncAttributeMaxDynamicSharedMemorySize, CfgBig::SMEM + TRASH);
-        attr_done[dev][var] = true;
-    }
-    hipLaunchKernelGGL(table[var], dim3((unsigned)(kp.tiles_m * kp.tiles_n)), dim3(512), CfgBig::SMEM + TRASH, s, kp);
-}
-
+enum { PIPE8 = 0, PIPE10 = 1 };    // igemm8_kernel, igemm10_kernel
 using CfgT320 = Cfg<4, 2, 4, 10>;   // 256 x 320: 64 x 160 per wave (igemm10_kernel)
-void launch10(const KParams& kp, hipStream_t s) {
-    static const pipe_kernel_t table[V_COUNT] = {igemm10_kernel<V_P0>, igemm10_kernel<V_P1>, igemm10_kernel<V_P2>, igemm10_kernel<V_EW>,
-                                                 igemm10_kernel<V_W0>, igemm10_kernel<V_W1>, igemm10_kernel<V_W2>, igemm10_kernel<V_G0>,
-                                                 igemm10_kernel<V_GEW>, igemm10_kernel<V_SPLITK>};
-    static bool attr_done[64][V_COUNT] = {};
+
+void launch_pipelined(int pipe, const KParams& kp, hipStream_t s) {
+    static const pipe_kernel_t table[2][V_COUNT] = {
+        {igemm8_kernel<V_P0>, igemm8_kernel<V_P1>, igemm8_kernel<V_P2>, igemm8_kernel<V_EW>, igemm8_kernel<V_W0>,
+         igemm8_kernel<V_W1>, igemm8_kernel<V_W2>, igemm8_kernel<V_G0>, igemm8_kernel<V_GEW>, nullptr},
+        {igemm10_kernel<V_P0>, igemm10_kernel<V_P1>, igemm10_kernel<V_P2>, igemm10_kernel<V_EW>, igemm10_kernel<V_W0>,
+         igemm10_kernel<V_W1>, igemm10_kernel<V_W2>, igemm10_kernel<V_G0>, igemm10_kernel<V_GEW>, igemm10_kernel<V_SPLITK>}};
+    static bool attr_done[64][2][V_COUNT] = {};
+    const int smem = (pipe == PIPE10 ? CfgT320::SMEM : CfgBig::SMEM) + TRASH;
     const int dev = pt_device(), var = kp.ws ? V_SPLITK : tail_variant(kp.p);
-    if (!attr_done[dev][var]) {
-        (void)hipFuncSetAttribute((const void*)table[var], hipFuncAttributeMaxDynamicSharedMemorySize, CfgT320::SMEM + TRASH);
-        attr_done[dev][var] = true;
+    if (!attr_done[dev][pipe][var]) {
+        (void)hipFuncSetAttribute((const void*)table[pipe][var], hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        attr_done[dev][pipe][var] = true;
     }
-    hipLaunchKernelGGL(table[var], dim3((unsigned)(kp.tiles_m * kp.tiles_n * kp.splits)), dim3(512), CfgT320::SMEM + TRASH, s, kp);
+    hipLaunchKernelGGL(table[pipe][var], dim3((unsigned)(kp.tiles_m * kp.tiles_n * kp.splits)), dim3(512), smem, s, kp);
 }
 
 // Process-wide hooks (single-threaded setters, read by every later plan).
@@ -1015,15 +958,15 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
         KParams k1 = kp;                                     // pass 1: bare products into the fp32 slabs
         k1.ws = (float*)p.splitk_ws; k1.splits = pl.splits;
         k1.p.bias = nullptr; k1.p.res = nullptr; k1.p.res_lo = nullptr; k1.p.out_lo = nullptr; k1.p.vec = nullptr; k1.p.blend = nullptr; k1.p.vec_mode = 0; k1.p.act = 0;
-        launch10(k1, s);
+        launch_pipelined(PIPE10, k1, s);
         KParams k2 = kp;                                     // pass 2: ordered sum + the whole epilogue
         k2.ws = (float*)p.splitk_ws; k2.splits = pl.splits;
         const long long work = (long long)p.M * (p.N / 8);
         long long blocks = (work + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k2);
-    } else if (pl.cfg == 3) launch10(kp, s);
-    else if (pl.cfg == 0 && pl.fast) launch8(kp, s);
+    } else if (pl.cfg == 3) launch_pipelined(PIPE10, kp, s);
+    else if (pl.cfg == 0 && pl.fast) launch_pipelined(PIPE8, kp, s);
     else if (pl.cfg == 0) launch<CfgBig, false>(kp, s);     // the plain loop for generic K
     else if (pl.cfg == 1) launch<CfgW320>(kp, pl.fast, s);
     else if (pl.cfg == 4) launch<CfgN160>(kp, pl.fast, s);

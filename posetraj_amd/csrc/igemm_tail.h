@@ -69,6 +69,20 @@ struct Cfg {
     static_assert((NT / 16) % 8 == 0, "row swizzle must be slot-group independent");
 };
 
+// LDS image of an operand tile (format: the comment at the top of igemm.hip): rows of 128 B, the eight 16-byte chunks of row r
+// XOR-swizzled by (r >> 1) & 7.  The functions below are the only places that spell it out.
+// Writer side: the LDS-DMA destination is lane-linear - thread t's copy lands in row t >> 3, physical chunk t & 7 - so the thread
+// fetches the logical chunk that belongs there.
+__device__ __forceinline__ int lds_src_chunk(int t) { return (t & 7) ^ ((t >> 4) & 7); }
+// Reader side: byte offset of logical chunk `chunk` inside row `row`; for the fragment reads, of the 32-deep k half ks of lane
+// (frow, fq) - fragment rows start at multiples of 16, so frow stands for the row.
+__device__ __forceinline__ int lds_chunk_off(int row, int chunk) { return (chunk ^ ((row >> 1) & 7)) * 16; }
+__device__ __forceinline__ int lds_khalf_off(int frow, int fq, int ks) { return lds_chunk_off(frow, fq + 4 * ks); }
+// Row order of a 64-row weight piece of the kernels whose waves are 160 columns wide: LDS row lr = (wave column s, fragment f, r) =
+// (lr >> 5, (lr >> 4) & 1, lr & 15) holds weight row 160 s + 16 f + r of the piece (piece j starts 32 j rows further).  (lr by
+// reference: by value, ffn320_kernel's scalar bookkeeping - nothing else - came out re-allocated.)
+__device__ __forceinline__ int lds_wpiece_row(const int& lr) { return (lr >> 5) * 160 + ((lr >> 4) & 1) * 16 + (lr & 15); }
+
 __device__ __forceinline__ int vec_index(const pt_igemm_params& p, int m) {
     if (p.vec_mode == 1) return m / p.vG;
     return ((m / p.vFS) * p.vS + m % p.vS) % p.vB;
@@ -101,7 +115,7 @@ template <class CF, int NEWER>
 __device__ __forceinline__ void bias_init(const f16x4 (&b4)[CF::TN], f32x4 (&acc)[CF::TN][CF::TM]) {
     // the bias loads are older than the NEWER LDS-DMA copies of the prologue issued since: a counted wait retires the
     // loads and leaves the copies in flight (their latency no longer queues behind the bias round trip)
-    __builtin_amdgcn_s_waitcnt(((NEWER & 15) | ((NEWER >> 4) << 14)) | 0x0F70);
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(NEWER));
 #pragma unroll
     for (int ni = 0; ni < CF::TN; ++ni) {
         const f32x4 b = {(float)b4[ni][0], (float)b4[ni][1], (float)b4[ni][2], (float)b4[ni][3]};
@@ -266,7 +280,7 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                 }
                 *(f32x4*)(E + (mi * 16 + frow) * ELD + ni * 16 + 4 * fq) = o;
             }
-        __builtin_amdgcn_s_waitcnt(0xC07F);                  // lgkmcnt(0): this wave's LDS writes have landed
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));           // this wave's LDS writes have landed
         if (rc < 4) ig_stamp(kp, wave, lane, 5 + 2 * rc);
         const int mc0 = mrow0 + rc * RH;
         if (fastpath) {
@@ -323,7 +337,7 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                 }
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);                  // reads done before the next chunk overwrites E
+        __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));           // reads done before the next chunk overwrites E
         if (rc < 4) ig_stamp(kp, wave, lane, 6 + 2 * rc);
     }
 }
@@ -360,7 +374,7 @@ __device__ __forceinline__ void igemm_epilogue(const KParams& kp, f32x4 (&acc)[C
     // ---------------- epilogue 2: the wave's full width, RH rows at a time, through LDS; row-wise fused tail.
     // every wave is done with the operand tiles.  Raw barrier: __syncthreads() would also drain the pipelined kernels'
     // past-the-end copies (still in flight towards the trash rows, carrying the side-input prefetch) with a vmcnt(0).
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     ig_stamp(kp, wave, lane, 4);

@@ -44,10 +44,6 @@ struct LParams {
 constexpr int L_SLOT = 16384, L_SMEM = 10 * L_SLOT;      // 160 KiB: the ring is the whole LDS
 constexpr int L_LN_OFF = 9 * L_SLOT;                     // gamma | beta lie in the slot that is first written in phase 1 of chunk 0, long after the prologue read them
 
-__device__ __forceinline__ void lq_swap16(uint32_t& a, uint32_t& b) {      // rows of 16 lanes: a's odd rows <-> b's even rows
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-
 // output stores a wave has issued in the seven phase slots behind slot tau = 5 c + p (a slot has one iff tau >= 5 and tau % 5 != 4)
 constexpr int lq_stores_behind(int tau) {
     int k = 0;
@@ -84,9 +80,8 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
     if (wave == 6) pt_glds16(lp.b + min(lane, 39) * 8, smem + L_LN_OFF + 1024);
 
     // ---------------- LDS-DMA set-up (as ffn320_kernel's W1 ring).  One copy per thread moves 8 KiB: LDS row t >> 3, physical chunk t & 7
-    const int swz = frow >> 1;
-    const int c0 = (fq ^ swz) * 16, c1 = ((fq + 4) ^ swz) * 16;                     // byte offsets of the two 32-deep k halves
-    const int csrc = (t & 7) ^ ((t >> 4) & 7);               // logical chunk a thread's copy stores (rows XOR-swizzled by (row >> 1) & 7)
+    const int c0 = lds_khalf_off(frow, fq, 0), c1 = lds_khalf_off(frow, fq, 1);     // byte offsets of the two 32-deep k halves
+    const int csrc = lds_src_chunk(t);                       // logical chunk a thread's copy stores
     const int lr = t >> 3;                                   // 0 .. 63
     const int woff = lr * lp.kpad + csrc * 8;                // + (128 c + 64 u) * kpad + 64 kt   (u = second copy)
     char* const dma0 = smem + wave * 1024;
@@ -151,7 +146,7 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
             rstd[r] = rsqrtf(fmaxf(var, 0.f) + lp.eps);
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                      // (gamma / beta of waves 5 and 6 have landed; so has everything else)
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // (gamma / beta of waves 5 and 6 have landed; so has everything else)
     __builtin_amdgcn_s_barrier();
     {
         const char* const gl = smem + L_LN_OFF + fq * 16;
@@ -185,11 +180,11 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
 #define LQ_PHASE_MMA(body0, body1)                                                             \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     __builtin_amdgcn_s_barrier();                                                              \
-    __builtin_amdgcn_s_waitcnt(0xC47F);                      /* lgkmcnt(4): the first k halves */ \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(4));               /* the first k halves */ \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     body0                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                         \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                        \
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     body1                                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -212,9 +207,8 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
     // stores are always whole in the columns (chunk c - 1 <= nch - 2 lies below N).
     // Counted over the slots behind a wait (lq_stores_behind, evaluated at compile time: the first three chunks are peeled, from the fourth
     // on the count is periodic):   chunk 0: 0 0 0 0 0   chunk 1: 0 1 2 3 4   chunk 2: 4 5 6 6 6   chunk >= 3: 5 5 6 6 6   (phases 0 .. 4)
-#define LQ_WAIT_IMM(n_) ((n_) < 16 ? (0x0F70 | (n_)) : (0x4F70 | ((n_) - 16)))                   /* s_waitcnt vmcnt(n): bits 3:0 and 15:14 */
 #define LQ_VMWAIT(pp, ci)                                                                      \
-    if (st_counted) { __builtin_amdgcn_s_waitcnt(LQ_WAIT_IMM(14 + lq_stores_behind(5 * (ci) + (pp)))); } else { __builtin_amdgcn_s_waitcnt(0x0F7E); }
+    if (st_counted) { __builtin_amdgcn_s_waitcnt(pt_vmcnt(14 + lq_stores_behind(5 * (ci) + (pp)))); } else { __builtin_amdgcn_s_waitcnt(pt_vmcnt(14)); }
     // the finished chunk: fp32 -> (x column scale) -> fp16, pairs of column blocks exchanged across the 16-lane rows -> four 16-byte
     // values per lane (ov[2 bp + r]), stored one per phase
     u32x4 ov[4];
@@ -227,8 +221,8 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
                 union { f16x4 h; uint32_t u[2]; } pa_, pb_;                                    \
                 pa_.h = (f16x4){(f16)(a_[0] * sc_), (f16)(a_[1] * sc_), (f16)(a_[2] * sc_), (f16)(a_[3] * sc_)}; \
                 pb_.h = (f16x4){(f16)(b_[0] * sc_), (f16)(b_[1] * sc_), (f16)(b_[2] * sc_), (f16)(b_[3] * sc_)}; \
-                lq_swap16(pa_.u[0], pb_.u[0]);                                                 \
-                lq_swap16(pa_.u[1], pb_.u[1]);                                                 \
+                pt_swap16(pa_.u[0], pb_.u[0]);                                                 \
+                pt_swap16(pa_.u[1], pb_.u[1]);                                                 \
                 ov[2 * bp_ + r_] = (u32x4){pa_.u[0], pa_.u[1], pb_.u[0], pb_.u[1]};            \
             }                                                                                  \
     }
@@ -300,10 +294,9 @@ __global__ __launch_bounds__(512, 2) void lnlin320_kernel(const LParams lp) {
 #undef LQ_READ_W
 #undef LQ_MMA
 #undef LQ_VMWAIT
-#undef LQ_WAIT_IMM
 #undef LQ_CONVERT
 #undef LQ_PUT
-    __builtin_amdgcn_s_waitcnt(0x0F70);                      // no LDS-DMA may outlive the wave
+    __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
 }
 
 }  // namespace

@@ -100,6 +100,37 @@ __device__ __forceinline__ void pt_glds4(const void* gsrc, void* lds_wave_base) 
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
 
+// s_waitcnt immediates.  gfx9 layout: vmcnt in bits 3:0 and 15:14 (0 .. 63), expcnt in 6:4, lgkmcnt in 11:8 (0 .. 15); a counter
+// left at its maximum is not waited for.  pt_vmcnt(n) / pt_lgkmcnt(n) wait for one counter and leave the others untouched.
+constexpr int pt_waitcnt(int vm, int lgkm) { return (vm & 15) | ((vm >> 4) << 14) | 0x0070 | (lgkm << 8); }
+constexpr int pt_vmcnt(int n) { return pt_waitcnt(n, 15); }
+constexpr int pt_lgkmcnt(int n) { return pt_waitcnt(63, n); }
+static_assert(pt_vmcnt(0) == 0x0F70 && pt_vmcnt(6) == 0x0F76 && pt_vmcnt(15) == 0x0F7F && pt_vmcnt(17) == 0x4F71, "vmcnt encoding");
+static_assert(pt_lgkmcnt(0) == 0xC07F && pt_lgkmcnt(8) == 0xC87F && pt_waitcnt(9, 0) == 0x0079, "lgkmcnt encoding");
+
+// ds_read_b64_tr_b16: per 16-lane group a 4-row x 16-column block of halfs, delivered column-major
+__device__ __forceinline__ f16x4 pt_lds_tr16(const void* p) {
+    typedef __fp16 hw_f16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+    const hw_f16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hw_f16x4*)p);
+    return __builtin_bit_cast(f16x4, v);
+}
+
+// Cross-lane exchanges without LDS: v_permlane32_swap exchanges the upper half of its first operand with the lower half of its
+// second (v_permlane16_swap: odd rows of 16 lanes with even rows), so with both operands holding v the two registers hold
+// {own, partner's} in every lane.  Written as inline asm: through __builtin_amdgcn_permlane32_swap hipcc (ROCm 7.2) used result 0
+// for both elements of the returned pair (max(r0, r1) compiled to r0 - every lane silently kept only the LOWER lane's value).
+// The s_nop covers the VALU-write -> permlane-read hazard (2 wait states) inside the statement.  T: any 32-bit register type.
+template <class T>
+__device__ __forceinline__ void pt_swap32(T& a, T& b) {                // a's upper 32 lanes <-> b's lower 32 lanes
+    static_assert(sizeof(T) == 4, "one VGPR");
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+template <class T>
+__device__ __forceinline__ void pt_swap16(T& a, T& b) {                // rows of 16 lanes: a's odd rows <-> b's even rows
+    static_assert(sizeof(T) == 4, "one VGPR");
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+
 __device__ __forceinline__ float pt_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -18,7 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "posetraj_amd", "csrc")
 
 
-def scan(src: str):
+def kernel_streams(src: str, csrc: str = None):
+    """Compile one source (hipcc -S, device only) and walk the assembly: {mangled kernel name: [instruction lines, comments stripped]}.
+    `csrc`: compile the file of that name in another tree's csrc directory (tools/isa_compare.py)."""
+    if csrc:
+        src = os.path.join(csrc, os.path.basename(src))
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
         r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S",
@@ -26,24 +30,33 @@ def scan(src: str):
         if r.returncode != 0:
             raise RuntimeError(r.stderr[-2000:])
         lines = open(out).read().splitlines()
-    stats, name, idx, last = {}, None, 0, -99
+    streams, name = {}, None
     for ln in lines:
         m = re.match(r"^(_Z\w+):", ln)
         if m:
-            name, idx, last = m.group(1), 0, -99
-            stats[name] = [0, 0]
+            name = m.group(1)
+            streams[name] = []
             continue
-        t = ln.strip()
-        if name is None or not t or t[0] in ".;":
-            continue
-        idx += 1
-        if t.startswith(("global_load", "buffer_load", "flat_load")):
-            stats[name][0] += 1
-            last = idx
-        elif t.startswith("s_waitcnt") and "vmcnt(0)" in t and idx - last <= 3:
-            stats[name][1] += 1
-        elif t.startswith("s_endpgm"):
+        if ln.startswith(".Lfunc_end"):                      # (not the first s_endpgm: a kernel with an early return has several)
             name = None
+        t = ln.split(";")[0].strip()
+        if name is None or not t or t[0] == ".":
+            continue
+        streams[name].append(t)
+    return {k: v for k, v in streams.items() if "s_endpgm" in v}          # (device variables have mangled labels too)
+
+
+def scan(src: str):
+    stats = {}
+    for name, stream in kernel_streams(src).items():
+        loads, waited, last = 0, 0, -99
+        for idx, t in enumerate(stream, 1):
+            if t.startswith(("global_load", "buffer_load", "flat_load")):
+                loads += 1
+                last = idx
+            elif t.startswith("s_waitcnt") and "vmcnt(0)" in t and idx - last <= 3:
+                waited += 1
+        stats[name] = [loads, waited]
     return stats
 
 
