@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 9
+#define PT_ABI_VERSION 10
 
 int         pt_abi_version(void);
 const char* pt_last_error(void);
@@ -453,6 +453,17 @@ int pt_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float 
  * copy of the parameters the next forward reads norm weights and biases from - and zero_grad != 0 clears g.  n % 4 == 0, 16-byte aligned. */
 int pt_adamw_fused_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, void* stream);
+/* --use_ema (round 7): pt_adamw_fused_f32 - the same statements, bit-identical p, m, v, mirror and g - that also takes one step of
+ * diffusers' EMAModel over the parameters it has just written (scripts/train_svd_traj_VIPSeg_14.py:1423-1430; diffusers 0.24.0
+ * training_utils.EMAModel.step): ema_shadow -= one_minus_decay * (ema_shadow - p_new), three separately rounded fp32 operations like
+ * torch's `s.sub_(omd * (s - p))`.  one_minus_decay = (float)(1.0 - decay), the subtraction in double.  ema_shadow: n floats, 16-byte aligned. */
+int pt_adamw_ema_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                     int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, float* ema_shadow, float one_minus_decay,
+                     void* stream);
+/* the EMA step alone (scripts/train_svd_traj_VIPSeg_14.py:1428-1430 on a step the GradScaler skipped: `ema.step` runs under
+ * `accelerator.sync_gradients` whether or not the optimizer moved; diffusers EMAModel.step): shadow -= one_minus_decay * (shadow - p).
+ * n % 4 == 0, 16-byte aligned. */
+int pt_ema_update_f32(float* shadow, const float* p, int64_t n, float one_minus_decay, void* stream);
 /* the fp16 operand pt_igemm_f16 streams, straight from the fp32 master weight w [T][Co][Ci] (tap-major: T = kh kw taps, 1 for a
  * linear layer - the layout the trainer keeps weights, gradients and Adam moments in, so that weight gradients are written
  * with unit stride):

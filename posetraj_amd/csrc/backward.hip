@@ -661,13 +661,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // The same update, four values per thread, and the two passes that follow an optimizer step in the trainer folded in (round 6): the fp16
 // mirror of the parameters (ParamStore.flat16: norm weights / biases are read from it) is written here instead of by a cast over the
 // whole buffer, and the gradient is zeroed here instead of by a fill - 5.4 GB of the step's 28 GB of optimizer traffic.
+//
+// EMA (round 7): diffusers' EMAModel.step over the same parameters (--use_ema; scripts/train_svd_traj_VIPSeg_14.py:1428-1430),
+//   shadow.sub_((1 - decay) * (shadow - param))   =   d = s - p ; t = omd d ; s = s - t      three separately rounded fp32 operations.
+// Left to itself the compiler contracts t and the last subtraction into one v_fma (the rounding intrinsics do not stop it), so the
+// statements sit under `fp contract(off)` - and only they: AdamW's own expressions keep the contraction they always had.
+__device__ __forceinline__ float ema_update(float s, float p, float omd) {
+#pragma clang fp contract(off)
+    const float d = s - p;
+    const float t = omd * d;
+    return s - t;
+}
+
+// EMA = true: the shadow follows the NEW parameter while it is still in a register (one more read and one more write of a buffer whose
+// neighbours are already here: 8 bytes per parameter on top of 34, against 12 for a launch of its own).
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                           int64_t n4, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                          float bc2_sqrt, float inv_scale, f16* __restrict__ mirror, int zero_g) {
+                                                          float bc2_sqrt, float inv_scale, f16* __restrict__ mirror, int zero_g,
+                                                          float* __restrict__ shadow, float omd) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const f32x4 g4 = *(const f32x4*)(g + 4 * i), m4 = *(const f32x4*)(m + 4 * i), v4 = *(const f32x4*)(v + 4 * i);
-        f32x4 p4 = *(const f32x4*)(p + 4 * i), mo, vo;
+        f32x4 p4 = *(const f32x4*)(p + 4 * i), mo, vo, s4;
         f16x4 h4;
+        if constexpr (EMA) s4 = *(const f32x4*)(shadow + 4 * i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float gi = g4[j] * inv_scale;
@@ -679,10 +696,23 @@ __global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p,
             pi -= (lr / bc1) * (mi / denom);
             p4[j] = pi;
             h4[j] = (f16)pi;
+            if constexpr (EMA) s4[j] = ema_update(s4[j], pi, omd);
         }
         *(f32x4*)(p + 4 * i) = p4; *(f32x4*)(m + 4 * i) = mo; *(f32x4*)(v + 4 * i) = vo;
         if (mirror) *(f16x4*)(mirror + 4 * i) = h4;
         if (zero_g) *(f32x4*)(g + 4 * i) = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if constexpr (EMA) *(f32x4*)(shadow + 4 * i) = s4;
+    }
+}
+
+// The EMA update alone: the step the GradScaler skipped (the shadow moves toward the unchanged parameters), and the stand-alone EMAModel.step()
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ shadow, const float* __restrict__ p, int64_t n4, float omd) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const f32x4 p4 = *(const f32x4*)(p + 4 * i);
+        f32x4 s4 = *(const f32x4*)(shadow + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s4[j] = ema_update(s4[j], p4[j], omd);
+        *(f32x4*)(shadow + 4 * i) = s4;
     }
 }
 
@@ -986,15 +1016,44 @@ extern "C" int pt_adamw_f32(float* p, const float* g, float* m, float* v, int64_
     return 0;
 }
 
+// one launcher for pt_adamw_fused_f32 (shadow == nullptr) and pt_adamw_ema_f32
+static int adamw_fused_launch(const char* who, float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, float* shadow,
+                              float one_minus_decay, void* stream) {
+    PT_CHECK(p && g && m && v && n > 0 && n % 4 == 0 && step >= 1, "%s: bad arguments (n must be a multiple of 4)", who);
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    PT_CHECK(al16(p) && al16(g) && al16(m) && al16(v) && al16(shadow) && (!half_mirror || ((uintptr_t)half_mirror & 7) == 0),
+             "%s: buffers must be 16-byte aligned", who);
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    if (shadow)
+        hipLaunchKernelGGL(adamw_fused_kernel<true>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, lr, beta1, beta2, eps,
+                           weight_decay, (float)bc1, (float)sqrt(bc2), inv_scale, (f16*)half_mirror, zero_grad, shadow, one_minus_decay);
+    else
+        hipLaunchKernelGGL(adamw_fused_kernel<false>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, lr, beta1, beta2, eps,
+                           weight_decay, (float)bc1, (float)sqrt(bc2), inv_scale, (f16*)half_mirror, zero_grad, (float*)nullptr, 0.0f);
+    PT_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int pt_adamw_fused_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                   int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, void* stream) {
-    PT_CHECK(p && g && m && v && n > 0 && n % 4 == 0 && step >= 1, "pt_adamw_fused_f32: bad arguments (n must be a multiple of 4)");
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    PT_CHECK(al16(p) && al16(g) && al16(m) && al16(v) && (!half_mirror || ((uintptr_t)half_mirror & 7) == 0), "pt_adamw_fused_f32: buffers must be 16-byte aligned");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adamw_fused_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, lr, beta1, beta2, eps, weight_decay,
-                       (float)bc1, (float)sqrt(bc2), inv_scale, (f16*)half_mirror, zero_grad);
-    PT_LAUNCH_CHECK("pt_adamw_fused_f32");
+    return adamw_fused_launch("pt_adamw_fused_f32", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, inv_scale, half_mirror, zero_grad, nullptr,
+                              0.0f, stream);
+}
+
+extern "C" int pt_adamw_ema_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, float* ema_shadow, float one_minus_decay,
+                                void* stream) {
+    PT_CHECK(ema_shadow && ema_shadow != p, "pt_adamw_ema_f32: ema_shadow must be a buffer of its own");
+    return adamw_fused_launch("pt_adamw_ema_f32", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, inv_scale, half_mirror, zero_grad, ema_shadow,
+                              one_minus_decay, stream);
+}
+
+extern "C" int pt_ema_update_f32(float* shadow, const float* p, int64_t n, float one_minus_decay, void* stream) {
+    PT_CHECK(shadow && p && shadow != p && n > 0 && n % 4 == 0, "pt_ema_update_f32: bad arguments (n must be a multiple of 4)");
+    PT_CHECK(((uintptr_t)shadow & 15) == 0 && ((uintptr_t)p & 15) == 0, "pt_ema_update_f32: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(ema_update_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n / 4, one_minus_decay);
+    PT_LAUNCH_CHECK("pt_ema_update_f32");
     return 0;
 }
 

@@ -68,6 +68,11 @@ def load_state_dict_file(path: str) -> Dict[str, torch.Tensor]:
     return load_file(path)
 
 
+# what diffusers' EMAModel.save_pretrained adds to the config.json of an averaged model (<checkpoint>/controlnet_ema/): not
+# constructor arguments - from_config drops them, so that from_pretrained(ckpt, subfolder="controlnet_ema") reads the averaged model
+EMA_CONFIG_KEYS = ("decay", "min_decay", "optimization_step", "update_after_step", "use_ema_warmup", "inv_gamma", "power")
+
+
 class HipModel:
     """Common surface of the two networks: config, weights in / out, device handling.
 
@@ -147,7 +152,7 @@ class HipModel:
 
     @classmethod
     def from_config(cls, config, **kw):
-        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_") and k not in EMA_CONFIG_KEYS}
         cfg.update(kw)
         return cls(**cfg)
 

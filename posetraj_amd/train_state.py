@@ -13,6 +13,10 @@ No tensor arithmetic happens here: files, counters and a scalar multiplier.  A c
                                      skipped-step count, the micro-batch position inside an accumulation cycle (always 0: states
                                      are saved after an optimizer step, like the reference does)
 
+    controlnet_ema/                  only with ``ControlNetTrainer(use_ema=True)``: the averaged weights in the same two files, the
+                                     seven ``EMAModel`` scalars added to ``config.json`` (diffusers' ``EMAModel.save_pretrained``);
+                                     ``trainer_state.json`` then carries them as ``"ema"`` too
+
 (the reference's ``optimizer.bin`` / ``scaler.pt`` / ``scheduler.bin`` are pickles of torch objects; the schedule here is a pure
 function of the step count and needs no file).
 """
@@ -133,15 +137,22 @@ def resume_position(checkpoint_path: str, gradient_accumulation_steps: int, num_
 
 
 # ------------------------------------------------------------------------------------------------- trainer state <-> files
-def save_controlnet(trainer, path: str) -> None:
-    """``controlnet.save_pretrained(path)``: config + the fp32 master parameters in the reference's state-dict format."""
+def save_model(config, tensors, path: str, extra: Optional[dict] = None) -> None:
+    """``model.save_pretrained(path)`` of a ControlNet given as config + named tensors; ``extra``: further ``config.json`` entries
+    (the EMA scalars of a ``controlnet_ema/`` folder)."""
     from safetensors.torch import save_file
     os.makedirs(path, exist_ok=True)
-    cfg = {k: v for k, v in dict(trainer.config).items() if not k.startswith("_")}
+    cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
     cfg["_class_name"] = "ControlNetSDVModel"
+    cfg.update(extra or {})
     with open(os.path.join(path, "config.json"), "w") as f:
         json.dump(cfg, f, indent=2)
-    save_file({k: v.cpu() for k, v in trainer.params.state_dict().items()}, os.path.join(path, "diffusion_pytorch_model.safetensors"))
+    save_file({k: v.cpu() for k, v in tensors.items()}, os.path.join(path, "diffusion_pytorch_model.safetensors"))
+
+
+def save_controlnet(trainer, path: str) -> None:
+    """``controlnet.save_pretrained(path)``: config + the fp32 master parameters in the reference's state-dict format."""
+    save_model(trainer.config, trainer.params.state_dict(), path)
 
 
 def save_state(trainer, output_dir: str) -> None:
@@ -163,6 +174,10 @@ def save_state(trainer, output_dir: str) -> None:
              "hyperparameters": {"learning_rate": trainer.lr, "adam_beta1": trainer.betas[0], "adam_beta2": trainer.betas[1],
                                  "adam_weight_decay": trainer.weight_decay, "adam_epsilon": trainer.eps,
                                  "gradient_accumulation_steps": trainer.accumulation}}
+    ema = getattr(trainer, "ema", None)
+    if ema is not None:                                                    # the save hook's `ema.save_pretrained` (:993-994)
+        ema.save_pretrained(os.path.join(output_dir, "controlnet_ema"))
+        state["ema"] = dict(ema.scalars(), cur_decay_value=ema.cur_decay_value)
     tmp = os.path.join(output_dir, "trainer_state.json.tmp")
     with open(tmp, "w") as f:
         json.dump(state, f, indent=2)
@@ -179,6 +194,11 @@ def load_state(trainer, input_dir: str) -> dict:
     if state.get("format") != 1:
         raise RuntimeError(f"{input_dir}: unknown trainer_state format {state.get('format')!r}")
     P = trainer.params
+    ema = getattr(trainer, "ema", None)
+    ema_dir = os.path.join(input_dir, "controlnet_ema")
+    if ema is not None and not os.path.isdir(ema_dir):                     # (a trainer without EMA ignores the folder, as the script does without the flag)
+        raise RuntimeError(f"{input_dir}: the trainer has use_ema=True but the checkpoint has no controlnet_ema/ folder "
+                           "(it was written by a run without EMA)")
     weights = load_file(os.path.join(input_dir, "controlnet", "diffusion_pytorch_model.safetensors"))
     moments = load_file(os.path.join(input_dir, "optimizer.safetensors"))
     P.load(P.flat, weights)
@@ -189,4 +209,11 @@ def load_state(trainer, input_dir: str) -> dict:
     trainer.optimizer_steps, trainer.skipped_steps = int(state["optimizer_steps"]), int(state["skipped_steps"])
     trainer.loss_scale, trainer._clean = float(state["loss_scale"]), int(state["growth_tracker"])
     trainer._micro, trainer._accum_scale = 0, None
+    if ema is not None:                                                    # the load hook (:1003-1006): shadow and counters
+        with open(os.path.join(ema_dir, "config.json")) as f:
+            cfg = json.load(f)
+        from .modeling import EMA_CONFIG_KEYS
+        ema.load_state_dict(dict({k: cfg[k] for k in EMA_CONFIG_KEYS if k in cfg},
+                                 shadow_params=load_file(os.path.join(ema_dir, "diffusion_pytorch_model.safetensors"))))
+        ema.cur_decay_value = (state.get("ema") or {}).get("cur_decay_value", ema.cur_decay_value)
     return state

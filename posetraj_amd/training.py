@@ -7,7 +7,9 @@ inference kernels - and the whole step: ``ControlNetTrainer`` runs the forward o
 update (``pt_adamw_f32``) with fp16-mixed-precision loss scaling and gradient accumulation as ``accelerate`` does them for
 ``start_ft.sh``.  The VAE encode (``tensor_to_vae_latent``, ``:495-503``) and the CLIP embedding of the first frame are this
 package's own models; their outputs are the step's inputs.  The camera twin (``controlnet_sdv_cam``, ``scripts/train_svd_traj_VIPSeg_14_cam_concat.py``: the same step with
-``camera_cond`` and without the spatial loss) trains through the same class.  Not here: EMA (``--use_ema``, off in the launch scripts), the 8-bit
+``camera_cond`` and without the spatial loss) trains through the same class.  ``--use_ema`` (off in the launch scripts) is
+``ControlNetTrainer(use_ema=True)``: diffusers' ``EMAModel`` over the ControlNet's parameters (``training_utils.py``), stepped inside
+the optimizer's pass.  Not here: the 8-bit
 optimizer (bitsandbytes), gradient checkpointing (activations of one 14-frame clip fit the 288 GB many times over), the data
 loader.
 """
@@ -212,6 +214,14 @@ class ControlNetTrainer:
     package's layer and pack objects) for ~45 ms and frees nothing (profiles/r04/train_step_host_gc.txt).  Frozen, the
     long-lived objects are out of the collector's way; cyclic garbage among them would no longer be reclaimed (there is none).
 
+    ``use_ema`` (``--use_ema``; ``ema_*``: the arguments of diffusers' ``EMAModel``, ``:970-974``): ``trainer.ema`` is a
+    ``training_utils.EMAModel`` over the parameters - one more flat fp32 buffer - and ``optimizer_step`` OWNS its step: the loop does not
+    call ``ema.step`` (``:1430``) as well.  The reference steps the EMA under ``accelerator.sync_gradients``, i.e. once per accumulation
+    cycle whether or not the GradScaler skipped the optimizer: on a taken step the update is part of the AdamW launch
+    (``pt_adamw_ema_f32``: the shadow follows the new parameter while it is in a register), on a skipped one it is ``pt_ema_update_f32``
+    toward the unchanged parameters.  ``ema_state_dict()``: the averaged weights, for a validation pipeline or the final export.
+    Data parallel: every rank keeps its own, identical shadow.  ``None`` (the default): no buffer, no launch, nothing in a checkpoint.
+
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
 
@@ -221,7 +231,8 @@ class ControlNetTrainer:
                  scaling_factor: float = 0.18215, conditioning_dropout_prob: Optional[float] = None, process_group=None,
                  bucket_mb: int = 256, wgrad_stream: bool = True, spatial_stream: bool = True, freeze_gc: bool = False,
                  lr_scheduler=None, use_graph: bool = False, device_scalars: Optional[bool] = None, encoder_stream: bool = True,
-                 pack_stream: bool = True):
+                 pack_stream: bool = True, use_ema: bool = False, ema_decay: float = 0.9999, ema_min_decay: float = 0.0,
+                 ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3):
         from . import autodiff as AD
         from . import grad_sync
         from . import train_graph as TG
@@ -249,6 +260,11 @@ class ControlNetTrainer:
         grad_sync.broadcast_parameters(self.params.flat, process_group)
         self.buckets = grad_sync.GradientBuckets(self.params.grad, self.params.spans(), process_group, bucket_bytes=bucket_mb << 20)
         self.world = self.buckets.world
+        self.ema = None                                   # (after the broadcast: the shadow starts as a clone of rank 0's parameters everywhere)
+        if use_ema:
+            from .training_utils import EMAModel
+            self.ema = EMAModel(self.params, decay=ema_decay, min_decay=ema_min_decay, update_after_step=ema_update_after_step,
+                                use_ema_warmup=use_ema_warmup, inv_gamma=ema_inv_gamma, power=ema_power, model_config=cfg)
         if self.world > 1:
             self.params.on_grad_ready = self.buckets.mark_ready
         # use_graph: forward + backward of a step replayed as ONE hipGraph (see loss_and_grads); device_scalars (implied by it): the
@@ -487,6 +503,8 @@ class ControlNetTrainer:
             raise RuntimeError("ControlNetTrainer.optimizer_step: no gradients accumulated since the last step")
         norm = self.grad_norm() if grad_norm is None else grad_norm
         took = math.isfinite(norm)
+        ema = self.ema
+        omd = ema.begin_step() if ema is not None else None          # EMAModel.step's counter and decay: taken or skipped (:1428-1430)
         if took:
             if self.lr_scheduler is not None:            # LambdaLR: the rate of step k (0-based) is base x lambda(k); a skipped step
                 self.last_lr = self.lr * float(self.lr_scheduler(self.optimizer_steps))          # does not advance the schedule
@@ -495,10 +513,14 @@ class ControlNetTrainer:
             self.optimizer_steps += 1
             P = self.params
             # AdamW + the fp16 mirror of the new parameters + the gradient's zeroing in ONE pass over the buffers
-            hip.check(hip.lib().pt_adamw_fused_f32(P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel,
-                                                   self.last_lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.optimizer_steps,
-                                                   1.0 / (self._accum_scale * self.world), P.flat16.data_ptr(), 1, ops._stream()),
-                      "pt_adamw_fused_f32")
+            adamw = (P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel, self.last_lr, self.betas[0],
+                     self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, 1.0 / (self._accum_scale * self.world), P.flat16.data_ptr(), 1)
+            if ema is not None and self.ema_fused:        # ... and the EMA of the new parameters in the same pass
+                hip.check(hip.lib().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream()), "pt_adamw_ema_f32")
+            else:
+                hip.check(hip.lib().pt_adamw_fused_f32(*adamw, ops._stream()), "pt_adamw_fused_f32")
+                if ema is not None:
+                    ema.update(omd)
             P.version += 1
             P._mirror_version = P.version                 # (half_view() need not cast the buffer again)
             if self.pack_stream and self._packs_built and not self.use_graph:
@@ -516,6 +538,8 @@ class ControlNetTrainer:
         else:
             self.skipped_steps += 1
             self.loss_scale, self._clean = self.loss_scale * 0.5, 0
+            if ema is not None:                           # the shadow moves toward the unchanged parameters
+                ema.update(omd)
         if not took:
             self.params.zero_grad()
         self._micro, self._accum_scale = 0, None
@@ -531,6 +555,17 @@ class ControlNetTrainer:
             out["grad_norm"] = self.grad_norm()
             out["stepped"] = self.optimizer_step(out["grad_norm"])
         return out
+
+    # EMA on a taken step: inside the AdamW launch (True) or as pt_ema_update_f32 behind pt_adamw_fused_f32 (False) - the same numbers
+    # either way; tools/train_step_bench.py --ema {fused,separate} runs both.  Measured at 682 M parameters: 6.00 ms against 4.84 + 1.69
+    # (profiles/r07/train_step_ema_ab.txt)
+    ema_fused = True
+
+    def ema_state_dict(self) -> dict:
+        """The averaged weights by parameter name (fp32): what a validation pipeline or the final export loads under ``--use_ema``."""
+        if self.ema is None:
+            raise RuntimeError("ControlNetTrainer.ema_state_dict: the trainer was built with use_ema=False")
+        return self.ema.shadow_state_dict()
 
     def state_dict(self) -> dict:
         """The ControlNet's current fp32 parameters (``controlnet.save_pretrained`` of ``:1440-1470`` writes these)."""

@@ -4,7 +4,10 @@
 first frame (encode_image), rasterise the trajectory maps, run ControlNetTrainer.step for a few iterations, save the ControlNet
 with save_pretrained, load it back into the inference class and run one denoising call with it; with --checkpointing-steps the
 loop writes checkpoint-<global_step> folders (accelerator.save_state), rotates them (--checkpoints-total-limit) and a second
-invocation with --resume-from-checkpoint latest continues where the first stopped (:1224-1247).
+invocation with --resume-from-checkpoint latest continues where the first stopped (:1224-1247).  --use-ema: the trainer keeps the
+EMA of the ControlNet (ControlNetTrainer(use_ema=True) steps it: the script's line :1430 has no counterpart here), every
+--validation-steps the reference's validation swap runs (:1477-1480 store + copy_to, the pipeline on the averaged weights, :1540-1542
+restore), and the final model is the averaged one (:1558-1559 copy_to before save_pretrained).
 
     python tools/run_training_example.py [--steps 6] [--height 320 --width 576] [--tiny] [--out gpurun_out/controlnet_trained]
         [--svd-dir <stable-video-diffusion-img2vid dir> [--controlnet-dir <dir with controlnet/>]]
@@ -27,6 +30,7 @@ ap.add_argument("--svd-dir"); ap.add_argument("--controlnet-dir")
 ap.add_argument("--lr-scheduler", default="constant"); ap.add_argument("--lr-warmup-steps", type=int, default=500)
 ap.add_argument("--checkpointing-steps", type=int, default=0); ap.add_argument("--checkpoints-total-limit", type=int)
 ap.add_argument("--resume-from-checkpoint")
+ap.add_argument("--use-ema", action="store_true"); ap.add_argument("--validation-steps", type=int, default=0)
 ap.add_argument("--graph", action="store_true", help="ControlNetTrainer(use_graph=True): the step replayed as a hipGraph (needs --accumulation 1)")
 a = ap.parse_args()
 from posetraj_amd import train_state
@@ -49,7 +53,7 @@ else:
     clip = CLIPVisionModelWithProjection(**clip_cfg).init_random_(seed=4, device=dev)
     controlnet = ControlNetSDVModel.from_unet(unet, conditioning_embedding_out_channels=ce)                      # :935-938
 max_train_steps = max(1, a.steps // a.accumulation)
-trainer = ControlNetTrainer(controlnet.config, controlnet.state_dict(), unet, learning_rate=1e-5, freeze_gc=True, gradient_accumulation_steps=a.accumulation, use_graph=a.graph,
+trainer = ControlNetTrainer(controlnet.config, controlnet.state_dict(), unet, learning_rate=1e-5, freeze_gc=True, gradient_accumulation_steps=a.accumulation, use_graph=a.graph, use_ema=a.use_ema,
                             conditioning_dropout_prob=0.1, scaling_factor=vae.config.scaling_factor,
                             lr_scheduler=train_state.get_scheduler(a.lr_scheduler, a.lr_warmup_steps, max_train_steps, lr_init=1e-5))    # :1109-1114
 global_step, first_it = 0, 0
@@ -83,6 +87,16 @@ for it in range(a.steps):
             t2 = time.time()
             trainer.save_state(os.path.join(a.out, f"checkpoint-{global_step}"))
             print(f"  saved state to {a.out}/checkpoint-{global_step} in {time.time() - t2:.1f} s" + (f" (removed {', '.join(gone)})" if gone else ""))
+        if a.use_ema and (global_step % a.validation_steps == 0 if a.validation_steps else global_step == max_train_steps):
+            trainer.ema.store(); trainer.ema.copy_to()       # :1477-1480: validate with the averaged weights
+            pipe.controlnet = ControlNetSDVModel(**{k: v for k, v in dict(controlnet.config).items() if not k.startswith("_")}).load_state_dict(trainer.state_dict(), dev)
+            val = pipe(pixel_values[0, 0].add(1).div(2).unsqueeze(0).cpu(), maps, height=a.height, width=a.width, num_frames=a.frames, decode_chunk_size=8,
+                       num_inference_steps=2, output_type="pt").frames
+            trainer.ema.restore()                            # :1540-1542
+            print(f"  validation with the EMA weights (decay {trainer.ema.cur_decay_value:.4f} after {trainer.ema.optimization_step} EMA steps): "
+                  f"frames {tuple(val[0].shape)}, finite {bool(torch.isfinite(val[0]).all())}")
+if a.use_ema:
+    trainer.ema.copy_to()                                    # :1558-1559: the saved model is the averaged one
 # checkpoint (:1440-1470) and back into the inference class
 trained = ControlNetSDVModel(**{k: v for k, v in dict(controlnet.config).items() if not k.startswith("_")}).load_state_dict(trainer.state_dict(), dev, keep_source=True)
 trained.save_pretrained(os.path.join(a.out, "controlnet"))

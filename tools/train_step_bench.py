@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="ControlNetTrainer(use_graph=True): forward + backward replayed as a hipGraph (one per spatial "
                                                        "frame index, all captured before the timed steps)")
     ap.add_argument("--no-wgrad-stream", action="store_true"); ap.add_argument("--no-encoder-stream", action="store_true"); ap.add_argument("--no-spatial-stream", action="store_true"); ap.add_argument("--no-pack-stream", action="store_true")
+    ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off",
+                    help="ControlNetTrainer(use_ema=True): the EMA inside the AdamW launch (pt_adamw_ema_f32) or as pt_ema_update_f32 behind pt_adamw_fused_f32")
     ap.add_argument("--json", action="store_true", help="bench.py's train_step leg: time the steps without hipEvent brackets (median), count the matrix "
                                                       "flops in one extra bracketed step, print ONE JSON object")
     a = ap.parse_args()
@@ -56,8 +58,11 @@ def main():
     ccfg = dict(cn.config)
     del cn
     tr = ControlNetTrainer(ccfg, sd, unet, learning_rate=1e-5, conditioning_dropout_prob=0.1, freeze_gc=True, use_graph=a.graph,
-                           wgrad_stream=not a.no_wgrad_stream, encoder_stream=not a.no_encoder_stream, spatial_stream=not a.no_spatial_stream, pack_stream=not a.no_pack_stream)
-    print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + 2 Adam moments)")
+                           wgrad_stream=not a.no_wgrad_stream, encoder_stream=not a.no_encoder_stream, spatial_stream=not a.no_spatial_stream, pack_stream=not a.no_pack_stream,
+                           use_ema=a.ema != "off")
+    tr.ema_fused = a.ema != "separate"
+    print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + 2 Adam moments"
+          f"{' + EMA shadow, ' + a.ema if a.ema != 'off' else ''})")
     h, w = a.height // 8, a.width // 8
     D = unet.config.cross_attention_dim
     lat = torch.randn(1, a.frames, 4, h, w, generator=g) * 0.18215 * 5
@@ -110,7 +115,7 @@ def main():
                           "matrix_TFLOP_per_step": round(flops / 1e12, 2), "peak_device_GiB": round(peak, 1),
                           "trainable_params_M": round(tr.params.numel / 1e6, 1), "loss_finite": bool(out["loss"] == out["loss"]),
                           "optimizer_stepped": bool(out["stepped"]), "hipgraph": bool(a.graph), "step_graphs": n_graphs,
-                          "graph_replays_in_timed_steps": int(sum(replayed)),
+                          "graph_replays_in_timed_steps": int(sum(replayed)), **({"ema": a.ema} if a.ema != "off" else {}),
                           "host_gc_in_timed_steps": [g for g in gc_log if g[1] >= 1.0], "streams": 1 + int(tr.wgrad_stream) + int(tr.spatial_stream and not a.no_spatial) + int(tr.encoder_stream)}))
         return
     L.pt_prof_enable(1)
