@@ -96,7 +96,7 @@ def gemm(A, B, Cm, M, N, K, sa, sb, sc, *, nb=(1, 1, 1), ba=(0, 0, 0), bb=(0, 0,
     p.alpha, p.out_mode, p.splits = float(alpha), out_mode, splits
     if gather is not None:
         (p.g_H, p.g_W, p.g_OH, p.g_OW, p.g_KH, p.g_KW, p.g_stride, p.g_pad_h, p.g_pad_w, p.g_ld) = gather
-    hip.check(hip.lib().pt_gemm_f16(C.byref(p), _stream()), "pt_gemm_f16")
+    hip.checked().pt_gemm_f16(C.byref(p), _stream())
     if GEMM_LOG is not None:
         GEMM_LOG.append((M, N, K, nb[0] * nb[1] * nb[2], "T" if sa[0] == 1 else "N", "T" if sb[1] == 1 else "N", out_mode, splits, gather is not None))
 
@@ -113,15 +113,14 @@ def gemv(x: torch.Tensor, pw: Packed, res: Optional[torch.Tensor] = None) -> tor
     """``pt_gemv_f16``: a linear layer over at most 16 rows."""
     M = x.shape[0]
     out = torch.empty((M, pw.N), dtype=torch.float16, device=x.device)
-    hip.check(hip.lib().pt_gemv_f16(x.data_ptr(), x.stride(0), M, pw.w.data_ptr(), pw.Kpad, pw.K, pw.N, _ptr(pw.bias), _ptr(res),
-                                    0 if res is None else res.stride(0), out.data_ptr(), pw.N, _stream()), "pt_gemv_f16")
+    hip.checked().pt_gemv_f16(x.data_ptr(), x.stride(0), M, pw.w.data_ptr(), pw.Kpad, pw.K, pw.N, _ptr(pw.bias), _ptr(res),
+                              0 if res is None else res.stride(0), out.data_ptr(), pw.N, _stream())
     return out
 
 
 def colsum(dy: torch.Tensor, rows_per_seg: int, nseg: int, out: torch.Tensor, ncols: Optional[int] = None) -> None:
     """``out[seg, c] += sum_rows dy`` (fp32 ``out``)."""
-    hip.check(hip.lib().pt_colsum_f16(dy.data_ptr(), rows_per_seg, nseg, ncols or dy.shape[-1], dy.stride(-2), out.data_ptr(), _stream()),
-              "pt_colsum_f16")
+    hip.checked().pt_colsum_f16(dy.data_ptr(), rows_per_seg, nseg, ncols or dy.shape[-1], dy.stride(-2), out.data_ptr(), _stream())
 
 
 def _split_k(tiles: int, K: int) -> int:
@@ -186,8 +185,8 @@ class ParamStore:
     def refresh_alphas(self) -> None:
         """``alphas[i] = sigmoid(scalar i)`` from the fp32 master buffer; enqueued at the start of every step in device-scalar mode."""
         if self._scalar_names:
-            hip.check(hip.lib().pt_sigmoid_gather_f32(self.flat.data_ptr(), self._scalar_index.data_ptr(), len(self._scalar_names),
-                                                      self.alphas.data_ptr(), _stream()), "pt_sigmoid_gather_f32")
+            hip.checked().pt_sigmoid_gather_f32(self.flat.data_ptr(), self._scalar_index.data_ptr(), len(self._scalar_names),
+                                                self.alphas.data_ptr(), _stream())
 
     def alpha_ptr(self, k) -> int:
         return self.alphas.data_ptr() + 4 * self._alpha_slot[k]
@@ -355,9 +354,9 @@ class Dense:
         else:
             cpf, cpt = Ci, Co
         b = None if self.bname is None else self.P.value(self.bname)
-        L = hip.lib()
-        hip.check(L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 0, _ptr(b), f.w.data_ptr(), f.Kpad, cpf, _ptr(f.bias), _stream()), "pt_pack_weight_f32")
-        hip.check(L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 1, None, t.w.data_ptr(), t.Kpad, cpt, None, _stream()), "pt_pack_weight_f32")
+        L = hip.checked()
+        L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 0, _ptr(b), f.w.data_ptr(), f.Kpad, cpf, _ptr(f.bias), _stream())
+        L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 1, None, t.w.data_ptr(), t.Kpad, cpt, None, _stream())
 
     def _raw(self, buf):
         """The weight's flat (tap-major) slice of ``buf`` and its (T, Co, Ci); stacked layers: the adjacent matrices as one."""
@@ -502,13 +501,13 @@ def dense(tape: Tape, x: Var, L: Dense, *, geom=None, res: Optional[Var] = None,
             if upsample2x:
                 du = ops.igemm(dy, tp, geom=(Nimg, 2 * H, 2 * W))
                 d = torch.empty((Nimg * H * W, du.shape[-1]), dtype=torch.float16, device=du.device)
-                hip.check(hip.lib().pt_sumpool2x_f16(du.data_ptr(), Nimg, H, W, du.shape[-1], d.data_ptr(), _stream()), "pt_sumpool2x_f16")
+                hip.checked().pt_sumpool2x_f16(du.data_ptr(), Nimg, H, W, du.shape[-1], d.data_ptr(), _stream())
                 gx = [d]
             elif L.stride == 2:
                 OH, OW = (H + 2 * L.padding - 3) // 2 + 1, (W + 2 * L.padding - 3) // 2 + 1
                 Co = dy.shape[-1]
                 z = torch.empty((Nimg * H * W, Co), dtype=torch.float16, device=dy.device)
-                hip.check(hip.lib().pt_zero_insert2x_f16(dy.data_ptr(), Nimg, OH, OW, H, W, Co, z.data_ptr(), _stream()), "pt_zero_insert2x_f16")
+                hip.checked().pt_zero_insert2x_f16(dy.data_ptr(), Nimg, OH, OW, H, W, Co, z.data_ptr(), _stream())
                 gx = [ops.igemm(z, tp, geom=(Nimg, H, W))]
             elif x1 is None:
                 gx = [ops.igemm(dy, tp, geom=geom)]
@@ -540,9 +539,9 @@ def groupnorm(tape: Tape, x: Var, A: Affine, *, rows_per_sample: int, n_samples:
         dx1 = None if x1 is None else torch.empty((rows, C1), dtype=torch.float16, device=dy.device)
         stat = torch.empty(4 * n_samples * groups, dtype=torch.float32, device=dy.device)
         dg, db = A.grads()
-        hip.check(hip.lib().pt_groupnorm_bwd(x.v.data_ptr(), _ptr(None if x1 is None else x1.v), C0, C1, groups, rows_per_sample, n_samples, float(eps),
-                                             gm.data_ptr(), bt.data_ptr(), 1 if silu else 0, dy.data_ptr(), dx0.data_ptr(), _ptr(dx1), _ptr(dg), _ptr(db),
-                                             stat.data_ptr(), _stream()), "pt_groupnorm_bwd")
+        hip.checked().pt_groupnorm_bwd(x.v.data_ptr(), _ptr(None if x1 is None else x1.v), C0, C1, groups, rows_per_sample, n_samples, float(eps),
+                                       gm.data_ptr(), bt.data_ptr(), 1 if silu else 0, dy.data_ptr(), dx0.data_ptr(), _ptr(dx1), _ptr(dg), _ptr(db),
+                                       stat.data_ptr(), _stream())
         A.P.grad_ready(A.w, A.b)
         _acc(x, dx0)
         if x1 is not None:
@@ -564,8 +563,8 @@ def layernorm(tape: Tape, x: Var, A: Affine, eps: float = 1e-5) -> Var:
         dx = torch.empty_like(x.v)
         dg, db = A.grads()
         rowstat = None if dg is None else torch.empty(2 * M, dtype=torch.float32, device=dy.device)
-        hip.check(hip.lib().pt_layernorm_bwd(x.v.data_ptr(), M, Cc, gm.data_ptr(), float(eps), dy.data_ptr(), dx.data_ptr(), _ptr(dg), _ptr(db),
-                                             _ptr(rowstat), _stream()), "pt_layernorm_bwd")
+        hip.checked().pt_layernorm_bwd(x.v.data_ptr(), M, Cc, gm.data_ptr(), float(eps), dy.data_ptr(), dx.data_ptr(), _ptr(dg), _ptr(db),
+                                       _ptr(rowstat), _stream())
         A.P.grad_ready(A.w, A.b)
         _acc(x, dx)
 
@@ -581,7 +580,7 @@ def silu(tape: Tape, x: Var) -> Var:
         if dy is None or not x.need:
             return
         dx = torch.empty_like(x.v)
-        hip.check(hip.lib().pt_silu_bwd(x.v.data_ptr(), dy.data_ptr(), x.v.numel(), dx.data_ptr(), _stream()), "pt_silu_bwd")
+        hip.checked().pt_silu_bwd(x.v.data_ptr(), dy.data_ptr(), x.v.numel(), dx.data_ptr(), _stream())
         _acc(x, dx)
 
     tape.record(bwd)
@@ -593,7 +592,7 @@ def geglu(tape: Tape, h: Var) -> Var:
     M, two_i = h.v.shape
     I = two_i // 2
     y = torch.empty((M, I), dtype=torch.float16, device=h.v.device)
-    hip.check(hip.lib().pt_geglu_f16(h.v.data_ptr(), M, I, y.data_ptr(), _stream()), "pt_geglu_f16")
+    hip.checked().pt_geglu_f16(h.v.data_ptr(), M, I, y.data_ptr(), _stream())
     out = Var(y)
 
     def bwd():
@@ -601,7 +600,7 @@ def geglu(tape: Tape, h: Var) -> Var:
         if dy is None:
             return
         dh = torch.empty_like(h.v)
-        hip.check(hip.lib().pt_geglu_bwd(h.v.data_ptr(), dy.data_ptr(), M, I, dh.data_ptr(), _stream()), "pt_geglu_bwd")
+        hip.checked().pt_geglu_bwd(h.v.data_ptr(), dy.data_ptr(), M, I, dh.data_ptr(), _stream())
         _acc(h, dh)
 
     tape.record(bwd)
@@ -639,7 +638,7 @@ def add_rowvec(tape: Tape, x: Var, vec: Var, rows_per_vec: int) -> Var:
     """``y[r] = x[r] + vec[r // rows_per_vec]`` (time-embedding rows, collapsed cross-attention, frame position embedding)."""
     rows, Cc = x.v.shape
     y = torch.empty_like(x.v)
-    hip.check(hip.lib().pt_add_rowvec_f16(x.v.data_ptr(), vec.v.data_ptr(), rows, Cc, rows_per_vec, y.data_ptr(), _stream()), "pt_add_rowvec_f16")
+    hip.checked().pt_add_rowvec_f16(x.v.data_ptr(), vec.v.data_ptr(), rows, Cc, rows_per_vec, y.data_ptr(), _stream())
     out = Var(y)
 
     def bwd():
@@ -664,22 +663,21 @@ def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
         # the weight changes with every optimizer step: read from device memory (ParamStore.alphas), so that the launch can be replayed
         # inside a captured hipGraph (ControlNetTrainer(use_graph=True)); the frozen U-Net's weights below are constants of the capture
         ap = M.P.alpha_ptr(M.name)
-        L = hip.lib()
-        hip.check(L.pt_lerp_f16_dev(a.v.data_ptr(), b.v.data_ptr(), ap, a.v.numel(), y.data_ptr(), _stream()), "pt_lerp_f16_dev")
+        L = hip.checked()
+        L.pt_lerp_f16_dev(a.v.data_ptr(), b.v.data_ptr(), ap, a.v.numel(), y.data_ptr(), _stream())
         out = Var(y)
 
         def scaled(dy, one_minus):
             d = dy.contiguous()
             z = torch.empty_like(d)
-            hip.check(L.pt_scale_f16_dev(d.data_ptr(), ap, one_minus, d.numel(), z.data_ptr(), _stream()), "pt_scale_f16_dev")
+            L.pt_scale_f16_dev(d.data_ptr(), ap, one_minus, d.numel(), z.data_ptr(), _stream())
             return z
 
         def bwd_dev():
             dy, out.g = out.g, None
             if dy is None:
                 return
-            hip.check(L.pt_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, M.P.gradient(M.name).data_ptr(), _stream()),
-                      "pt_dot_diff_dev")
+            L.pt_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, M.P.gradient(M.name).data_ptr(), _stream())
             M.P.grad_ready(M.name)
             _acc(a, scaled(dy, 0))
             _acc(b, scaled(dy, 1))
@@ -687,7 +685,7 @@ def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
         tape.record(bwd_dev)
         return out
     al = M.alpha()
-    hip.check(hip.lib().pt_lerp_f16(a.v.data_ptr(), b.v.data_ptr(), al, a.v.numel(), y.data_ptr(), _stream()), "pt_lerp_f16")
+    hip.checked().pt_lerp_f16(a.v.data_ptr(), b.v.data_ptr(), al, a.v.numel(), y.data_ptr(), _stream())
     out = Var(y)
 
     def bwd():
@@ -695,8 +693,8 @@ def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
         if dy is None:
             return
         if M.P.trainable:                                       # d alpha / d mix = alpha (1 - alpha)
-            hip.check(hip.lib().pt_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al),
-                                            M.P.gradient(M.name).data_ptr(), _stream()), "pt_dot_diff")
+            hip.checked().pt_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al),
+                                      M.P.gradient(M.name).data_ptr(), _stream())
             M.P.grad_ready(M.name)
         _acc(a, ops.scale(dy, al))
         _acc(b, ops.scale(dy, 1.0 - al))
@@ -726,7 +724,7 @@ def add_rows(x: Var, r0: int, r1: int, dy: torch.Tensor) -> None:
         return
     x.g = torch.zeros_like(x.v) if x.g is None else x.g.clone()
     sl = x.g[r0:r1]
-    hip.check(hip.lib().pt_axpy_f16(sl.data_ptr(), dy.data_ptr(), 1.0, sl.data_ptr(), sl.numel(), _stream()), "pt_axpy_f16")
+    hip.checked().pt_axpy_f16(sl.data_ptr(), dy.data_ptr(), 1.0, sl.data_ptr(), sl.numel(), _stream())
 
 
 def rows(tape: Tape, x: Var, r0: int, r1: int, defer: Optional[list] = None) -> Var:
@@ -747,7 +745,7 @@ def rows(tape: Tape, x: Var, r0: int, r1: int, defer: Optional[list] = None) -> 
         else:
             x.g = x.g.clone()
         sl = x.g[r0:r1]
-        hip.check(hip.lib().pt_axpy_f16(sl.data_ptr(), dy.data_ptr(), 1.0, sl.data_ptr(), sl.numel(), _stream()), "pt_axpy_f16")
+        hip.checked().pt_axpy_f16(sl.data_ptr(), dy.data_ptr(), 1.0, sl.data_ptr(), sl.numel(), _stream())
 
     tape.record(bwd)
     return out
@@ -775,13 +773,13 @@ def _attention_backward(qkv: torch.Tensor, dout: torch.Tensor, Cc: int, heads: i
         q0, k0, v0 = row0 * ld, row0 * ld + Cc, row0 * ld + 2 * Cc
         # S = scale Q K^T
         gemm((qkv, q0), (qkv, k0), (sc, 0), Sx, Sx, hd, (tok * ld, 1), (1, tok * ld), (Sx, 1), nb=nb, ba=bq, bb=bq, bc=bs, alpha=scale, out_mode=1)
-        hip.check(hip.lib().pt_softmax_rows(sc.data_ptr(), nbt * Sx, Sx, Sx, P.data_ptr(), Sx, _stream()), "pt_softmax_rows")
+        hip.checked().pt_softmax_rows(sc.data_ptr(), nbt * Sx, Sx, Sx, P.data_ptr(), Sx, _stream())
         # dV = P^T dO
         gemm((P, 0), (dout, row0 * ldo), (dqkv, v0), Sx, hd, Sx, (1, Sx), (tok * ldo, 1), (tok * ld, 1), nb=nb, ba=bs, bb=bo, bc=bq)
         # dP = dO V^T  (into the score buffer)
         gemm((dout, row0 * ldo), (qkv, v0), (sc, 0), Sx, Sx, hd, (tok * ldo, 1), (1, tok * ld), (Sx, 1), nb=nb, ba=bo, bb=bq, bc=bs, out_mode=1)
         dS = torch.empty_like(P)
-        hip.check(hip.lib().pt_softmax_bwd_rows(P.data_ptr(), Sx, sc.data_ptr(), Sx, nbt * Sx, Sx, dS.data_ptr(), Sx, _stream()), "pt_softmax_bwd_rows")
+        hip.checked().pt_softmax_bwd_rows(P.data_ptr(), Sx, sc.data_ptr(), Sx, nbt * Sx, Sx, dS.data_ptr(), Sx, _stream())
         # dQ = scale dS K ; dK = scale dS^T Q
         gemm((dS, 0), (qkv, k0), (dqkv, q0), Sx, hd, Sx, (Sx, 1), (tok * ld, 1), (tok * ld, 1), nb=nb, ba=bs, bb=bq, bc=bq, alpha=scale)
         gemm((dS, 0), (qkv, q0), (dqkv, k0), Sx, hd, Sx, (1, Sx), (tok * ld, 1), (tok * ld, 1), nb=nb, ba=bs, bb=bq, bc=bq, alpha=scale)
@@ -803,8 +801,8 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
         y = torch.empty((N * S, Cc), dtype=torch.float16, device=qkv.v.device)
         lse = torch.empty((N * S, heads), dtype=torch.float32, device=qkv.v.device)
         p0 = qkv.v.data_ptr()
-        hip.check(hip.lib().pt_attn_fwd_lse_f16(p0, ld, p0 + 2 * Cc, ld, p0 + 4 * Cc, ld, y.data_ptr(), Cc, N, S, S, heads, hd, hd ** -0.5,
-                                                lse.data_ptr(), _stream()), "pt_attn_fwd_lse_f16")
+        hip.checked().pt_attn_fwd_lse_f16(p0, ld, p0 + 2 * Cc, ld, p0 + 4 * Cc, ld, y.data_ptr(), Cc, N, S, S, heads, hd, hd ** -0.5,
+                                          lse.data_ptr(), _stream())
     elif hd == 64:
         y = ops.attn_spatial(qkv.v, N, S, heads, hd)
     else:
@@ -822,9 +820,8 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
         dqkv = torch.empty_like(qkv.v)
         dot = torch.empty((N * S, heads), dtype=torch.float32, device=dy.device)
         p0, d0 = qkv.v.data_ptr(), dqkv.data_ptr()
-        hip.check(hip.lib().pt_attn_bwd_f16(p0, ld, p0 + 2 * Cc, ld, p0 + 4 * Cc, ld, out.v.data_ptr(), Cc, dy.data_ptr(), dy.stride(0), lse.data_ptr(),
-                                            dot.data_ptr(), d0, d0 + 2 * Cc, d0 + 4 * Cc, dqkv.stride(0), N, S, heads, hd, hd ** -0.5, _stream()),
-                  "pt_attn_bwd_f16")
+        hip.checked().pt_attn_bwd_f16(p0, ld, p0 + 2 * Cc, ld, p0 + 4 * Cc, ld, out.v.data_ptr(), Cc, dy.data_ptr(), dy.stride(0), lse.data_ptr(),
+                                      dot.data_ptr(), d0, d0 + 2 * Cc, d0 + 4 * Cc, dqkv.stride(0), N, S, heads, hd, hd ** -0.5, _stream())
         _acc(qkv, dqkv)
 
     tape.record(bwd)
@@ -847,8 +844,8 @@ def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: 
             return
         if FLASH_BACKWARD and F <= 16 and hd in (64, 128):
             dqkv = torch.empty_like(qkv.v)
-            hip.check(hip.lib().pt_attn_temporal_bwd_f16(qkv.v.data_ptr(), qkv.v.stride(0), Cc, 2 * Cc, dy.data_ptr(), dy.stride(0), dqkv.data_ptr(),
-                                                         dqkv.stride(0), B, F, S, heads, hd, hd ** -0.5, _stream()), "pt_attn_temporal_bwd_f16")
+            hip.checked().pt_attn_temporal_bwd_f16(qkv.v.data_ptr(), qkv.v.stride(0), Cc, 2 * Cc, dy.data_ptr(), dy.stride(0), dqkv.data_ptr(),
+                                                   dqkv.stride(0), B, F, S, heads, hd, hd ** -0.5, _stream())
             _acc(qkv, dqkv)
             return
         _acc(qkv, _attention_backward(qkv.v, dy, Cc, heads, hd, F, S, (B, F * S, S, 1), 1))

@@ -220,15 +220,15 @@ class AutoencoderKLTemporalDecoder(HipModel):
         p.Nimg, p.Hin, p.Win, p.Hout, p.Wout, p.Ci, p.Co = N, H, W, Ho, Wo, Ci, Co
         p.KH, p.KW, p.stride, p.pad_h, p.pad_w = kh, kw, stride, pad, pad
         p.ldx, p.ldw, p.ldo, p.ldr, p.scale = x.stride(2), w.stride(0), Co, (Co if res is not None else 0), float(scale)
-        hip.check(hip.lib().pt_conv2d_f32(C.byref(p), ops._stream()), "pt_conv2d_f32")
+        hip.checked().pt_conv2d_f32(C.byref(p), ops._stream())
         return out
 
     def _gn32(self, x, gb, silu, eps=1e-6):
         N, H, W, Cc = x.shape
         y = torch.empty_like(x)
         st = torch.empty(2 * N * NORM_GROUPS, dtype=torch.float64, device=x.device)
-        hip.check(hip.lib().pt_groupnorm_f32(x.data_ptr(), H * W, N, Cc, NORM_GROUPS, eps, gb[0].data_ptr(), gb[1].data_ptr(), 1 if silu else 0,
-                                             st.data_ptr(), y.data_ptr(), ops._stream()), "pt_groupnorm_f32")
+        hip.checked().pt_groupnorm_f32(x.data_ptr(), H * W, N, Cc, NORM_GROUPS, eps, gb[0].data_ptr(), gb[1].data_ptr(), 1 if silu else 0,
+                                       st.data_ptr(), y.data_ptr(), ops._stream())
         return y
 
     def _res32(self, x, r):
@@ -244,7 +244,7 @@ class AutoencoderKLTemporalDecoder(HipModel):
         outs = []
         for i in range(N):                                     # one frame at a time: S x S fp32 scores (340 MB at 576 x 1024)
             sc = self._conv32(q[i].view(S, 1, 1, Cc), (k[i], None, (1, 1))).view(S, S)
-            hip.check(hip.lib().pt_softmax_rows_f32(sc.data_ptr(), S, S, S, Cc ** -0.5, ops._stream()), "pt_softmax_rows_f32")
+            hip.checked().pt_softmax_rows_f32(sc.data_ptr(), S, S, S, Cc ** -0.5, ops._stream())
             outs.append(self._conv32(sc.view(S, 1, 1, S), (v[i].t().contiguous(), None, (1, 1))).view(S, Cc))
         o = torch.stack(outs).view(N * S, 1, 1, Cc)
         return self._conv32(o, a["o"], res=x.reshape(N * S, 1, 1, Cc)).view(N, H, W, Cc)

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,200 +15,85 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.abspath(os.environ["PT_LIB"]) if os.environ.get("PT_LIB") else os.path.join(HERE, "libposetraj_hip.so")   # PT_LIB: A/B against another build on one box
 SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip"]
 HEADERS = ["pt_common.h", "igemm_tail.h"]
-ABI_VERSION = 10
+HEADER = os.path.join(HERE, "..", "include", "posetraj_hip.h")
+STRUCT_CLASSES = {"pt_igemm_params": "IgemmParams", "pt_ffn_params": "FfnParams", "pt_lnlin_params": "LnLinParams",
+                  "pt_conv_f32_params": "ConvF32Params", "pt_gemm_params": "GemmParams"}
 
-_lib = None
+_lib = _checked = None
 
-
-class IgemmParams(C.Structure):
-    """Mirror of ``pt_igemm_params`` (include/posetraj_hip.h)."""
-    _fields_ = [
-        ("x0", C.c_void_p), ("x1", C.c_void_p),
-        ("C0", C.c_int32), ("C1", C.c_int32), ("ld0", C.c_int32), ("ld1", C.c_int32),
-        ("Nimg", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("Hout", C.c_int32), ("Wout", C.c_int32),
-        ("KH", C.c_int32), ("KW", C.c_int32), ("stride", C.c_int32), ("pad_h", C.c_int32), ("pad_w", C.c_int32),
-        ("upsample2x", C.c_int32),
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("Kpad", C.c_int32),
-        ("w", C.c_void_p), ("bias", C.c_void_p),
-        ("out", C.c_void_p), ("ldo", C.c_int32),
-        ("res", C.c_void_p), ("ldr", C.c_int32),
-        ("vec", C.c_void_p), ("ldv", C.c_int32), ("vec_mode", C.c_int32), ("vG", C.c_int32), ("vFS", C.c_int32),
-        ("vS", C.c_int32), ("vB", C.c_int32),
-        ("blend", C.c_void_p), ("ldb", C.c_int32), ("alpha", C.c_float),
-        ("out_scale", C.c_float), ("act", C.c_int32), ("res_post", C.c_int32), ("out_f32", C.c_int32),
-        ("cs_cols", C.c_int32), ("cs_scale", C.c_float),
-        ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64),
-        ("res_lo", C.c_void_p), ("out_lo", C.c_void_p),
-    ]
+# ---------------------------------------------------------------------------------------------------------------------
+# The header is the only description of the ABI: the parameter structs, the signature table and the version below are
+# read from it at import (the C subset it uses, nothing more; tests/test_host_cpu.py has a C++ compiler confirm the reading).
+# ---------------------------------------------------------------------------------------------------------------------
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_TYPE = r"(?:const\s+)?\w+\s*\*?"
+_DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
+                            | (?P<ret>%s)\s*\b(?P<fn>pt_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
+                            | extern\s+"C"\s*\{ | \} )""" % _TYPE, re.X)
+_FIELD = re.compile(r"(%s)\s*\b(\w+(?:\s*,\s*\w+)*)" % _TYPE)         # `int32_t C0, C1`, `const void* x0`; a parameter is the one-name case
 
 
-class FfnParams(C.Structure):
-    """Mirror of ``pt_ffn_params`` (include/posetraj_hip.h)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("ldx", C.c_int32),
-        ("M", C.c_int32), ("C", C.c_int32), ("inner", C.c_int32),
-        ("w1", C.c_void_p), ("b1", C.c_void_p), ("kpad1", C.c_int32),
-        ("w2", C.c_void_p), ("b2", C.c_void_p), ("kpad2", C.c_int32),
-        ("out", C.c_void_p), ("ldo", C.c_int32),
-        ("res", C.c_void_p), ("ldr", C.c_int32),
-        ("vec", C.c_void_p), ("ldv", C.c_int32), ("vec_mode", C.c_int32), ("vG", C.c_int32), ("vFS", C.c_int32),
-        ("vS", C.c_int32), ("vB", C.c_int32),
-        ("blend", C.c_void_p), ("ldb", C.c_int32), ("alpha", C.c_float),
-        ("pre_w", C.c_void_p), ("pre_b", C.c_void_p), ("pre_kpad", C.c_int32),
-        ("pre_res", C.c_void_p), ("pre_ldr", C.c_int32),
-        ("pre_vec", C.c_void_p), ("pre_ldv", C.c_int32), ("pre_vec_mode", C.c_int32), ("pre_vG", C.c_int32), ("pre_vFS", C.c_int32),
-        ("pre_vS", C.c_int32), ("pre_vB", C.c_int32),
-        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float),
-    ]
+def _ctype(spelling: str, structs: dict, returned: bool = False):
+    """ctypes type of a C type as the header spells it: scalars by name, `const pt_X_params*` a pointer to that struct,
+    a returned `const char*` a string, every other pointer c_void_p."""
+    m = re.fullmatch(r"(const\s+)?(\w+)\s*(\*)?", spelling)
+    const, base, ptr = m.groups() if m else (None, None, None)
+    if not ptr and not const and base in _SCALARS:
+        return _SCALARS[base]
+    if ptr and const and base in structs:
+        return C.POINTER(structs[base])
+    if ptr and const and base == "char" and returned:
+        return C.c_char_p
+    if ptr and (base == "void" or base in _SCALARS):
+        return C.c_void_p
+    raise ValueError(f"posetraj_hip.h: type {spelling!r} is outside the C subset posetraj_amd.hip reads")
 
 
-class LnLinParams(C.Structure):
-    """Mirror of ``pt_lnlin_params`` (include/posetraj_hip.h)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("ldx", C.c_int32),
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("w", C.c_void_p), ("kpad", C.c_int32),
-        ("bias", C.c_void_p),
-        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float),
-        ("out", C.c_void_p), ("ldo", C.c_int32),
-        ("cs_cols", C.c_int32), ("cs_scale", C.c_float),
-    ]
+def _declarators(text: str, sep: str):
+    """[(C type, name)] of a struct body (sep ';', several names per type allowed) or a parameter list (sep ',')."""
+    out = []
+    for decl in filter(None, (d.strip() for d in text.split(sep))):
+        m = _FIELD.fullmatch(decl)
+        if not m or (sep == "," and "," in m.group(2)):
+            raise ValueError(f"posetraj_hip.h: cannot read the declaration {decl!r}")
+        out += [(" ".join(m.group(1).split()), n.strip()) for n in m.group(2).split(",")]
+    return out
 
 
-class ConvF32Params(C.Structure):
-    """Mirror of ``pt_conv_f32_params`` (include/posetraj_hip.h)."""
-    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("out", C.c_void_p)] + \
-               [(n, C.c_int32) for n in ("Nimg", "Hin", "Win", "Hout", "Wout", "Ci", "Co", "KH", "KW", "stride", "pad_h", "pad_w",
-                                         "ldx", "ldw", "ldo", "ldr")] + [("scale", C.c_float)]
+def _parse_header(text: str):
+    """(PT_ABI_VERSION, {struct tag: Structure class}, {entry point: (C return type, [C parameter types])}).  Raises on
+    anything it does not understand; no declaration is skipped."""
+    version = re.search(r"^#define\s+PT_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    if not version:
+        raise ValueError("posetraj_hip.h: no `#define PT_ABI_VERSION n`")
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    structs, protos, pos = {}, {}, 0
+    while text[pos:].strip():
+        m = _DECL.match(text, pos)
+        if not m:
+            raise ValueError(f"posetraj_hip.h: cannot read the declaration {text[pos:].strip().split(';')[0][:200]!r}")
+        if m.group("tag"):
+            tag = m.group("tag")
+            if tag not in STRUCT_CLASSES:
+                raise ValueError(f"posetraj_hip.h: struct {tag!r} has no class name in posetraj_amd.hip.STRUCT_CLASSES")
+            fields = [(n, _ctype(t, structs)) for t, n in _declarators(m.group("body"), ";")]
+            structs[tag] = type(STRUCT_CLASSES[tag], (C.Structure,), {"_fields_": fields, "__doc__": f"``{tag}`` of include/posetraj_hip.h."})
+        elif m.group("fn"):
+            params = m.group("params").strip()
+            protos[m.group("fn")] = (" ".join(m.group("ret").split()), [] if params == "void" else [t for t, _ in _declarators(params, ",")])
+        pos = m.end()
+    named = re.findall(r"pt_[a-z0-9_]+\s*\(", text)
+    if len(named) != len(protos):
+        raise ValueError(f"posetraj_hip.h: {len(named)} names are followed by '(' but {len(protos)} prototypes were read")
+    return int(version.group(1)), structs, protos
 
 
-class GemmParams(C.Structure):
-    """Mirror of ``pt_gemm_params`` (include/posetraj_hip.h)."""
-    _fields_ = [
-        ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
-        ("M", C.c_int32), ("N", C.c_int32),
-        ("K", C.c_int64),
-        ("sa_m", C.c_int64), ("sa_k", C.c_int64), ("sb_k", C.c_int64), ("sb_n", C.c_int64), ("sc_m", C.c_int64), ("sc_n", C.c_int64),
-        ("nb0", C.c_int32), ("nb1", C.c_int32), ("nb2", C.c_int32), ("out_mode", C.c_int32),
-        ("ba0", C.c_int64), ("ba1", C.c_int64), ("ba2", C.c_int64), ("bb0", C.c_int64), ("bb1", C.c_int64), ("bb2", C.c_int64),
-        ("bc0", C.c_int64), ("bc1", C.c_int64), ("bc2", C.c_int64),
-        ("alpha", C.c_float),
-        ("splits", C.c_int32),
-        ("g_H", C.c_int32), ("g_W", C.c_int32), ("g_OH", C.c_int32), ("g_OW", C.c_int32), ("g_KH", C.c_int32), ("g_KW", C.c_int32),
-        ("g_stride", C.c_int32), ("g_pad_h", C.c_int32), ("g_pad_w", C.c_int32), ("g_reserved", C.c_int32),
-        ("g_ld", C.c_int64),
-    ]
-
-
+with open(HEADER) as _f:
+    ABI_VERSION, _STRUCTS, PROTOTYPES = _parse_header(_f.read())       # PROTOTYPES: the C spelling, name -> (return type, [parameter types])
+IgemmParams, FfnParams, LnLinParams, ConvF32Params, GemmParams = (_STRUCTS[tag] for tag in STRUCT_CLASSES)         # in STRUCT_CLASSES' order
 # name -> (restype, argtypes); every symbol include/posetraj_hip.h declares
-SIGNATURES = {
-    "pt_abi_version": (C.c_int, []),
-    "pt_last_error": (C.c_char_p, []),
-    "pt_set_zero_page": (C.c_int, [C.c_void_p]),
-    "pt_igemm_f16": (C.c_int, [C.POINTER(IgemmParams), C.c_void_p]),
-    "pt_igemm_splitk_ws_bytes": (C.c_int64, [C.POINTER(IgemmParams)]),
-    "pt_ffn_geglu_f16": (C.c_int, [C.POINTER(FfnParams), C.c_void_p]),
-    "pt_ln_linear_f16": (C.c_int, [C.POINTER(LnLinParams), C.c_void_p]),
-    "pt_ln_linear_set_ablation": (C.c_int, [C.c_int32]),
-    "pt_conv2d_f32": (C.c_int, [C.POINTER(ConvF32Params), C.c_void_p]),
-    "pt_groupnorm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pt_softmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_float, C.c_void_p]),
-    "pt_igemm_force_config": (C.c_int, [C.c_int32]),
-    "pt_igemm_set_tuning": (C.c_int, [C.c_int32, C.c_int32]),
-    "pt_igemm_plan": (C.c_int, [C.POINTER(IgemmParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "pt_igemm_set_stamps": (C.c_int, [C.c_void_p, C.c_int64]),
-    "pt_groupnorm_scratch_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-    "pt_groupnorm_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
-                                     C.c_void_p, C.c_void_p]),
-    "pt_groupnorm_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_layernorm_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                   C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "pt_attn_spatial_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                      C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
-    "pt_attn_spatial_set_nqb": (C.c_int, [C.c_int32]),
-    "pt_attn_temporal_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "pt_attn_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "pt_vae_time_conv_out": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_frames_postprocess": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_nhwc_to_nchw_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_gaussian_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_patchify_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                  C.c_void_p]),
-    "pt_act_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
-    "pt_rasterize_tracks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                      C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_edm_train_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pt_edm_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
-                              C.c_void_p, C.c_void_p]),
-    "pt_gemm_f16": (C.c_int, [C.POINTER(GemmParams), C.c_void_p]),
-    "pt_attn_fwd_lse_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
-    "pt_attn_bwd_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                  C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "pt_attn_temporal_bwd_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "pt_groupnorm_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
-                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pt_layernorm_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "pt_colsum_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_softmax_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_softmax_bwd_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_geglu_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_geglu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_silu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_lerp_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_dot_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
-    "pt_lerp_f16_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_dot_diff_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pt_scale_f16_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_sigmoid_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_add_rowvec_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_sumpool2x_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_zero_insert2x_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_edm_loss_bwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
-                                  C.c_float, C.c_void_p, C.c_void_p]),
-    "pt_adamw_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                               C.c_float, C.c_int32, C.c_float, C.c_void_p]),
-    "pt_adamw_fused_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                     C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
-    "pt_adamw_ema_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                   C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]),
-    "pt_ema_update_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
-    "pt_sumsq_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "pt_pack_weight_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.c_void_p, C.c_void_p]),
-    "pt_gemv_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                              C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "pt_axpy_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_silu_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_timestep_embedding": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_nchw_to_nhwc_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                      C.c_void_p, C.c_void_p]),
-    "pt_nhwc_to_nchw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                  C.c_int32, C.c_void_p]),
-    "pt_concat_camera": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
-                                   C.c_void_p]),
-    "pt_scale_concat_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p]),
-    "pt_cfg_euler_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32,
-                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "pt_scale": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_euler_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int64,
-                                C.c_void_p]),
-    "pt_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "pt_resize_antialias_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pt_prof_enable": (C.c_int, [C.c_int32]),
-    "pt_prof_collect": (C.c_int, [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "pt_prof_collect_list": (C.c_int64, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64]),
-}
+SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in PROTOTYPES.items()}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -218,7 +104,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(HERE, "..", "include", "posetraj_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -275,7 +161,6 @@ def _write_resource_report(remarks: str) -> None:
     The pipelined igemm kernels live at the 256-register limit: a spill inside their K loop is a reload behind the LDS-DMA
     queue (tests/test_host_cpu.py asserts they have none)."""
     import json
-    import re
     out, cur = {}, None
     for line in remarks.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
@@ -296,27 +181,51 @@ def source_digest() -> str:
     to replay them for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", "posetraj_hip.h")]):
+    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER]):
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
     return h.hexdigest()
 
 
+def _load(errcheck=None):
+    """A handle of the library with every entry point typed from SIGNATURES; raises if it has not been built (no CPU
+    fallback exists).  With ``errcheck``, ctypes calls it on the result of every entry point that returns a status: return
+    type ``int`` in the header, pt_abi_version excepted."""
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "(posetraj_amd has no CPU or PyTorch fallback path)")
+    L = C.CDLL(LIB_PATH)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(L, name)            # AttributeError if the symbol is missing
+        fn.restype, fn.argtypes = res, args
+        if errcheck is not None and PROTOTYPES[name][0] == "int" and name != "pt_abi_version":
+            fn.errcheck = errcheck
+    if L.pt_abi_version() != ABI_VERSION:
+        raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} != expected {ABI_VERSION}; rebuild")
+    return L
+
+
 def lib():
-    """The loaded library; raises if it has not been built (no CPU fallback exists)."""
+    """The loaded library, raw: every call returns what the C function returned."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(posetraj_amd has no CPU or PyTorch fallback path)")
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)            # AttributeError if the symbol is missing
-            fn.restype, fn.argtypes = res, args
-        if L.pt_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} != expected {ABI_VERSION}; rebuild")
-        _lib = L
+        _lib = _load()
     return _lib
+
+
+def checked():
+    """The same library through a second handle whose status-returning entry points raise like ``check`` on a non-zero
+    status (ctypes' own ``errcheck``: no Python wrapper around the call).  What the product calls."""
+    global _checked
+    if _checked is None:
+        _checked = _load(_raise_on_status)
+    return _checked
+
+
+def _raise_on_status(rc, fn, args):
+    if rc != 0:
+        check(rc, fn.__name__)
+    return rc
 
 
 def check(rc: int, what: str = ""):

@@ -81,7 +81,7 @@ def ensure_ready(device) -> None:
     if idx not in _zero_pages:
         with torch.cuda.device(idx):
             z = torch.zeros(256, dtype=torch.uint8, device=device)
-            hip.check(hip.lib().pt_set_zero_page(z.data_ptr()), "pt_set_zero_page")
+            hip.checked().pt_set_zero_page(z.data_ptr())
         _zero_pages[idx] = z
 
 
@@ -182,11 +182,11 @@ def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, ge
     p.act = 1 if pw.geglu else (2 if pw.silu else 0)
     p.res_post, p.out_f32 = (1 if res_post else 0), (1 if out_f32 else 0)
     p.cs_cols, p.cs_scale = int(cs_cols), float(cs_scale)
-    need = hip.lib().pt_igemm_splitk_ws_bytes(C.byref(p))    # small-M layers: split-K through a caller-owned fp32 workspace
+    need = hip.checked().pt_igemm_splitk_ws_bytes(C.byref(p))    # small-M layers: split-K through a caller-owned fp32 workspace
     if need > 0 and splitk:
         ws = torch.empty(need // 4, dtype=torch.float32, device=x0.device)
         p.splitk_ws, p.splitk_ws_bytes = ws.data_ptr(), need
-    hip.check(hip.lib().pt_igemm_f16(C.byref(p), _stream()), "pt_igemm_f16")
+    hip.checked().pt_igemm_f16(C.byref(p), _stream())
     if explicit_out:
         _inplace_writes[out.data_ptr()] = _inplace_writes.get(out.data_ptr(), 0) + 1
     if out_lo is not None:
@@ -251,7 +251,7 @@ def ffn_geglu(x: torch.Tensor, w1: Packed, w2: Packed, *, res: Optional[torch.Te
             p.pre_vec, p.pre_ldv, p.pre_vec_mode = pv.data_ptr(), pv.stride(0), int(pre.get("vec_mode", 1))
             p.pre_vG, p.pre_vFS, p.pre_vS, p.pre_vB = int(pre.get("vG", 0)), int(pre.get("vFS", 0)), int(pre.get("vS", 0)), int(pre.get("vB", 0))
         p.ln_gamma, p.ln_beta, p.ln_eps = ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2]) if len(ln) > 2 else 1e-5
-    hip.check(hip.lib().pt_ffn_geglu_f16(C.byref(p), _stream()), "pt_ffn_geglu_f16")
+    hip.checked().pt_ffn_geglu_f16(C.byref(p), _stream())
     if Profiler.shapes is not None:
         Profiler.shapes.append((M, w2.N, w2.K, 1, 1, 1, 0, 0, 3, int(res is not None) + 2 * int(vec is not None) + 4 * int(blend is not None)
                                 + 32 * int(pre is not None)))              # 32: with the out-projection + LayerNorm prologue (its residual is a read too)
@@ -292,7 +292,7 @@ def ln_linear(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pw: Pack
     p.ln_gamma, p.ln_beta, p.ln_eps = gamma.data_ptr(), beta.data_ptr(), float(eps)
     p.out, p.ldo = out.data_ptr(), out.stride(0)
     p.cs_cols, p.cs_scale = int(cs_cols), float(cs_scale)
-    hip.check(hip.lib().pt_ln_linear_f16(C.byref(p), _stream()), "pt_ln_linear_f16")
+    hip.checked().pt_ln_linear_f16(C.byref(p), _stream())
     if Profiler.shapes is not None:
         Profiler.shapes.append((M, pw.N, pw.K, 1, 1, 1, 0, 0, 4, 0))        # act 4: LayerNorm in the prologue
     return out
@@ -307,16 +307,14 @@ def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, rows
     C1 = x1.shape[-1] if x1 is not None else 0
     Ct = C0 + C1
     rows = rows_per_sample * n_samples
-    L = hip.lib()
+    L = hip.checked()
     nfl = L.pt_groupnorm_scratch_floats(rows, Ct, n_samples)
     partials = torch.empty(nfl, dtype=torch.float32, device=x0.device)
     st = _stream()
-    hip.check(L.pt_groupnorm_stats(x0.data_ptr(), _ptr(x1), C0, C1, groups, rows_per_sample, n_samples, partials.data_ptr(), st),
-              "pt_groupnorm_stats")
+    L.pt_groupnorm_stats(x0.data_ptr(), _ptr(x1), C0, C1, groups, rows_per_sample, n_samples, partials.data_ptr(), st)
     y = torch.empty((rows, Ct), dtype=torch.float16, device=x0.device)
-    hip.check(L.pt_groupnorm_apply(x0.data_ptr(), _ptr(x1), C0, C1, groups, rows_per_sample, n_samples, float(eps),
-                                   gamma.data_ptr(), beta.data_ptr(), partials.data_ptr(), 1 if silu else 0, y.data_ptr(), st),
-              "pt_groupnorm_apply")
+    L.pt_groupnorm_apply(x0.data_ptr(), _ptr(x1), C0, C1, groups, rows_per_sample, n_samples, float(eps),
+                         gamma.data_ptr(), beta.data_ptr(), partials.data_ptr(), 1 if silu else 0, y.data_ptr(), st)
     return y
 
 
@@ -325,9 +323,9 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     _need(x, "x")
     M, Cc = x.shape
     y = torch.empty_like(x)
-    hip.check(hip.lib().pt_layernorm_f16(x.data_ptr(), M, Cc, _ptr(vec), (vec.stride(0) if vec is not None else 0),
-                                         1 if vec is not None else 0, vG, gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                         y.data_ptr(), _stream()), "pt_layernorm_f16")
+    hip.checked().pt_layernorm_f16(x.data_ptr(), M, Cc, _ptr(vec), (vec.stride(0) if vec is not None else 0),
+                                   1 if vec is not None else 0, vG, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                   y.data_ptr(), _stream())
     return y
 
 
@@ -337,9 +335,8 @@ def attn_spatial(qkv: torch.Tensor, Nimg: int, S: int, heads: int, head_dim: int
     _need(qkv, "qkv")
     Cc = heads * head_dim
     out = torch.empty((Nimg * S, Cc), dtype=torch.float16, device=qkv.device)
-    hip.check(hip.lib().pt_attn_spatial_f16(qkv.data_ptr(), qkv.stride(0), Cc, 2 * Cc, out.data_ptr(), Cc, Nimg, S,
-                                            heads, head_dim, head_dim ** -0.5, 1 if q_prescaled else 0, _stream()),
-              "pt_attn_spatial_f16")
+    hip.checked().pt_attn_spatial_f16(qkv.data_ptr(), qkv.stride(0), Cc, 2 * Cc, out.data_ptr(), Cc, Nimg, S,
+                                      heads, head_dim, head_dim ** -0.5, 1 if q_prescaled else 0, _stream())
     return out
 
 
@@ -357,8 +354,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nbatch: int, Sq
         raise RuntimeError(f"posetraj_amd.attention: shapes {tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)} for "
                            f"{nbatch} x ({Sq}, {Sk}) tokens of {heads} x {head_dim}")
     out = torch.empty((nbatch * Sq, Cc), dtype=torch.float16, device=q.device)
-    hip.check(hip.lib().pt_attn_f16(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-                                    out.data_ptr(), Cc, nbatch, Sq, Sk, heads, head_dim, head_dim ** -0.5, _stream()), "pt_attn_f16")
+    hip.checked().pt_attn_f16(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                              out.data_ptr(), Cc, nbatch, Sq, Sk, heads, head_dim, head_dim ** -0.5, _stream())
     return out
 
 
@@ -371,8 +368,8 @@ def attn_temporal(qkv: torch.Tensor, B: int, F: int, S: int, heads: int, head_di
     _need(qkv, "qkv")
     Cc = heads * head_dim
     out = torch.empty((B * F * S, Cc), dtype=torch.float16, device=qkv.device)
-    hip.check(hip.lib().pt_attn_temporal_f16(qkv.data_ptr(), qkv.stride(0), Cc, 2 * Cc, out.data_ptr(), Cc, B, F, S,
-                                             heads, head_dim, head_dim ** -0.5, _stream()), "pt_attn_temporal_f16")
+    hip.checked().pt_attn_temporal_f16(qkv.data_ptr(), qkv.stride(0), Cc, 2 * Cc, out.data_ptr(), Cc, B, F, S,
+                                       heads, head_dim, head_dim ** -0.5, _stream())
     return out
 
 
@@ -381,15 +378,14 @@ def axpy(a: torch.Tensor, r: torch.Tensor, m: float) -> torch.Tensor:
     if a.numel() != r.numel():
         raise RuntimeError(f"posetraj_amd.axpy: size mismatch {tuple(a.shape)} vs {tuple(r.shape)}")
     out = torch.empty_like(a)
-    hip.check(hip.lib().pt_axpy_f16(a.data_ptr(), r.data_ptr(), float(m), out.data_ptr(), a.numel(), _stream()),
-              "pt_axpy_f16")
+    hip.checked().pt_axpy_f16(a.data_ptr(), r.data_ptr(), float(m), out.data_ptr(), a.numel(), _stream())
     return out
 
 
 def silu(x: torch.Tensor) -> torch.Tensor:
     _need(x, "x")
     y = torch.empty_like(x)
-    hip.check(hip.lib().pt_silu_f16(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "pt_silu_f16")
+    hip.checked().pt_silu_f16(x.data_ptr(), y.data_ptr(), x.numel(), _stream())
     return y
 
 
@@ -397,7 +393,7 @@ def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     _need(t, "t", torch.float32)
     n = t.numel()
     out = torch.empty((n, dim), dtype=torch.float16, device=t.device)
-    hip.check(hip.lib().pt_timestep_embedding(t.data_ptr(), n, dim, out.data_ptr(), _stream()), "pt_timestep_embedding")
+    hip.checked().pt_timestep_embedding(t.data_ptr(), n, dim, out.data_ptr(), _stream())
     return out
 
 
@@ -415,8 +411,8 @@ def to_channels_last(x: torch.Tensor, cpad: Optional[int] = None) -> torch.Tenso
         x = x.float()
     x = x.contiguous()
     out = torch.empty((N, H, W, cpad), dtype=torch.float16, device=x.device)
-    hip.check(hip.lib().pt_nchw_to_nhwc_f16(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, N, Cc, H, W, cpad,
-                                            out.data_ptr(), _stream()), "pt_nchw_to_nhwc_f16")
+    hip.checked().pt_nchw_to_nhwc_f16(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, N, Cc, H, W, cpad,
+                                      out.data_ptr(), _stream())
     return out
 
 
@@ -426,8 +422,7 @@ def to_nchw(x: torch.Tensor, Cc: Optional[int] = None, f32: bool = False) -> tor
     N, H, W, ld = x.shape
     Cc = Cc or ld
     out = torch.empty((N, Cc, H, W), dtype=torch.float32 if f32 else torch.float16, device=x.device)
-    hip.check(hip.lib().pt_nhwc_to_nchw(x.data_ptr(), N, Cc, H, W, ld, out.data_ptr(), 1 if f32 else 0, _stream()),
-              "pt_nhwc_to_nchw")
+    hip.checked().pt_nhwc_to_nchw(x.data_ptr(), N, Cc, H, W, ld, out.data_ptr(), 1 if f32 else 0, _stream())
     return out
 
 
@@ -435,8 +430,7 @@ def concat_camera(feat: torch.Tensor, cam: torch.Tensor, cpad: int) -> torch.Ten
     _need(feat, "feat"); _need(cam, "cam")
     N, H, W, Cc = feat.shape
     out = torch.empty((N, H, W, cpad), dtype=torch.float16, device=feat.device)
-    hip.check(hip.lib().pt_concat_camera(feat.data_ptr(), Cc, cam.data_ptr(), N, H * W, cpad, out.data_ptr(), _stream()),
-              "pt_concat_camera")
+    hip.checked().pt_concat_camera(feat.data_ptr(), Cc, cam.data_ptr(), N, H * W, cpad, out.data_ptr(), _stream())
     return out
 
 
@@ -447,8 +441,8 @@ def scale_concat_input(latents: torch.Tensor, image_latents: torch.Tensor, sigma
     Bc, F, _, h, w = latents.shape
     if out is None:
         out = torch.empty((2 * Bc, F, h, w, 8), dtype=torch.float16, device=latents.device)
-    hip.check(hip.lib().pt_scale_concat_input(latents.data_ptr(), image_latents.data_ptr(), float(sigma), Bc, F, h, w,
-                                              out.data_ptr(), _stream()), "pt_scale_concat_input")
+    hip.checked().pt_scale_concat_input(latents.data_ptr(), image_latents.data_ptr(), float(sigma), Bc, F, h, w,
+                                        out.data_ptr(), _stream())
     return out
 
 
@@ -459,9 +453,8 @@ def cfg_euler_step(noise_pred: torch.Tensor, guidance: torch.Tensor, sigma: floa
     _need(noise_pred, "noise_pred", noise_pred.dtype if f32 else torch.float16)
     _need(latents, "latents", torch.float32); _need(guidance, "guidance", torch.float32)
     Bc, F, _, h, w = latents.shape
-    hip.check(hip.lib().pt_cfg_euler_step(noise_pred.data_ptr(), 1 if f32 else 0, noise_pred.stride(-2), guidance.data_ptr(), float(sigma),
-                                          float(sigma_next), prediction_type, Bc, F, h, w, latents.data_ptr(), _stream()),
-              "pt_cfg_euler_step")
+    hip.checked().pt_cfg_euler_step(noise_pred.data_ptr(), 1 if f32 else 0, noise_pred.stride(-2), guidance.data_ptr(), float(sigma),
+                                    float(sigma_next), prediction_type, Bc, F, h, w, latents.data_ptr(), _stream())
 
 
 def scale(x: torch.Tensor, k: float) -> torch.Tensor:
@@ -469,8 +462,8 @@ def scale(x: torch.Tensor, k: float) -> torch.Tensor:
         raise RuntimeError("posetraj_amd.scale: needs a fp16/fp32 tensor on the GPU (no CPU path exists)")
     x = x.contiguous()
     y = torch.empty_like(x)
-    hip.check(hip.lib().pt_scale(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, float(k), y.data_ptr(), x.numel(),
-                                 _stream()), "pt_scale")
+    hip.checked().pt_scale(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, float(k), y.data_ptr(), x.numel(),
+                           _stream())
     return y
 
 
@@ -482,9 +475,8 @@ def euler_step(model_output: torch.Tensor, sample_f32: torch.Tensor, sigma: floa
     mo = model_output.contiguous()
     x = sample_f32.contiguous()
     out = torch.empty_like(x)
-    hip.check(hip.lib().pt_euler_step(mo.data_ptr(), 1 if mo.dtype == torch.float32 else 0, x.data_ptr(), float(sigma),
-                                      float(sigma_next), prediction_type, out.data_ptr(), x.numel(), _stream()),
-              "pt_euler_step")
+    hip.checked().pt_euler_step(mo.data_ptr(), 1 if mo.dtype == torch.float32 else 0, x.data_ptr(), float(sigma),
+                                float(sigma_next), prediction_type, out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -497,9 +489,9 @@ def add_noise(x: torch.Tensor, noise: torch.Tensor, sigma_per_sample: torch.Tens
         raise RuntimeError(f"posetraj_amd.add_noise: shapes {tuple(x.shape)} / {tuple(noise.shape)} / {tuple(sigma_per_sample.shape)}")
     xc, nc = x.contiguous(), noise.contiguous()
     y = torch.empty_like(xc)
-    hip.check(hip.lib().pt_add_noise(xc.data_ptr(), nc.data_ptr(), 1 if x.dtype == torch.float32 else 0,
-                                     sigma_per_sample.contiguous().data_ptr(), xc.numel() // x.shape[0], y.data_ptr(),
-                                     xc.numel(), _stream()), "pt_add_noise")
+    hip.checked().pt_add_noise(xc.data_ptr(), nc.data_ptr(), 1 if x.dtype == torch.float32 else 0,
+                               sigma_per_sample.contiguous().data_ptr(), xc.numel() // x.shape[0], y.data_ptr(),
+                               xc.numel(), _stream())
     return y
 
 
@@ -526,8 +518,8 @@ def resize_with_antialiasing(image: torch.Tensor, size) -> torch.Tensor:
     x = image.contiguous()
     tmp = torch.empty(2 * x.numel(), dtype=torch.float32, device=x.device)
     out = torch.empty((B, Cc, oh, ow), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().pt_resize_antialias_f32(x.data_ptr(), B * Cc, H, W, oh, ow, tx.data_ptr(), ks[1], ty.data_ptr(), ks[0],
-                                                tmp.data_ptr(), out.data_ptr(), _stream()), "pt_resize_antialias_f32")
+    hip.checked().pt_resize_antialias_f32(x.data_ptr(), B * Cc, H, W, oh, ow, tx.data_ptr(), ks[1], ty.data_ptr(), ks[0],
+                                          tmp.data_ptr(), out.data_ptr(), _stream())
     return out
 
 
@@ -538,8 +530,8 @@ def patchify(image: torch.Tensor, patch: int, ld: int) -> torch.Tensor:
     x = image.contiguous()
     B, Cc, H, W = x.shape
     out = torch.empty((B * (H // patch) * (W // patch), ld), dtype=torch.float16, device=x.device)
-    hip.check(hip.lib().pt_patchify_f16(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, B, Cc, H, W, patch, ld, out.data_ptr(),
-                                        _stream()), "pt_patchify_f16")
+    hip.checked().pt_patchify_f16(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, B, Cc, H, W, patch, ld, out.data_ptr(),
+                                  _stream())
     return out
 
 
@@ -551,7 +543,7 @@ def activation(x: torch.Tensor, kind: str) -> torch.Tensor:
         raise ValueError(f"posetraj_amd.activation: hidden_act {kind!r} unsupported (gelu, quick_gelu)")
     xc = x.contiguous()
     y = torch.empty_like(xc)
-    hip.check(hip.lib().pt_act_f16(xc.data_ptr(), y.data_ptr(), xc.numel(), k, _stream()), "pt_act_f16")
+    hip.checked().pt_act_f16(xc.data_ptr(), y.data_ptr(), xc.numel(), k, _stream())
     return y
 
 
@@ -561,8 +553,7 @@ def vae_time_conv_out(x: torch.Tensor, w_host, b_host, F: int, HW: int, out: tor
     _need(x, "x", torch.float32); _need(out, "out", torch.float32)
     if x.dim() != 2 or x.shape[0] != F * HW or out.numel() != F * 3 * HW or not out.is_contiguous():
         raise RuntimeError(f"posetraj_amd.vae_time_conv_out: shapes {tuple(x.shape)} / {tuple(out.shape)} for {F} x {HW}")
-    hip.check(hip.lib().pt_vae_time_conv_out(x.data_ptr(), x.stride(0), w_host, b_host, F, HW, out.data_ptr(), _stream()),
-              "pt_vae_time_conv_out")
+    hip.checked().pt_vae_time_conv_out(x.data_ptr(), x.stride(0), w_host, b_host, F, HW, out.data_ptr(), _stream())
     return out
 
 
@@ -577,7 +568,7 @@ def frames_postprocess(clip: torch.Tensor, output_type: str) -> torch.Tensor:
     x = clip.contiguous()
     shape = (F, 3, H, W) if mode == 0 else (F, H, W, 3)
     out = torch.empty(shape, dtype=torch.uint8 if mode == 2 else torch.float32, device=x.device)
-    hip.check(hip.lib().pt_frames_postprocess(x.data_ptr(), F, H * W, mode, out.data_ptr(), _stream()), "pt_frames_postprocess")
+    hip.checked().pt_frames_postprocess(x.data_ptr(), F, H * W, mode, out.data_ptr(), _stream())
     return out
 
 
@@ -585,7 +576,7 @@ def to_nchw_f32(x: torch.Tensor, N: int, HW: int, Cc: int) -> torch.Tensor:
     """fp32 channels-last ``[N*HW, ld]`` -> fp32 ``[N, C, HW]``."""
     _need(x, "x", torch.float32)
     out = torch.empty((N, Cc, HW), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().pt_nhwc_to_nchw_f32(x.data_ptr(), N, Cc, HW, x.stride(0), out.data_ptr(), _stream()), "pt_nhwc_to_nchw_f32")
+    hip.checked().pt_nhwc_to_nchw_f32(x.data_ptr(), N, Cc, HW, x.stride(0), out.data_ptr(), _stream())
     return out
 
 
@@ -594,8 +585,8 @@ def gaussian_sample(params: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
     _need(params, "params", torch.float32); _need(noise, "noise", torch.float32)
     N, C2, h, w = params.shape
     out = torch.empty((N, C2 // 2, h, w), dtype=torch.float32, device=params.device)
-    hip.check(hip.lib().pt_gaussian_sample(params.contiguous().data_ptr(), noise.contiguous().data_ptr(), N, C2 // 2, h * w,
-                                           out.data_ptr(), _stream()), "pt_gaussian_sample")
+    hip.checked().pt_gaussian_sample(params.contiguous().data_ptr(), noise.contiguous().data_ptr(), N, C2 // 2, h * w,
+                                     out.data_ptr(), _stream())
     return out
 
 
@@ -605,16 +596,16 @@ class Profiler:
     shapes = None          # when a list: ops.igemm appends one shape tuple per launch (tools/shape_report.py)
 
     def __enter__(self):
-        hip.check(hip.lib().pt_prof_enable(1), "pt_prof_enable")
+        hip.checked().pt_prof_enable(1)
         return self
 
     def __exit__(self, *exc):
-        hip.check(hip.lib().pt_prof_enable(0), "pt_prof_enable")
+        hip.checked().pt_prof_enable(0)
 
     @staticmethod
     def collect_list(family: str, cap: int = 1 << 20):
         ms, fl = (C.c_double * cap)(), (C.c_double * cap)()
-        n = hip.lib().pt_prof_collect_list(Profiler.FAMILIES[family], ms, fl, cap)
+        n = hip.checked().pt_prof_collect_list(Profiler.FAMILIES[family], ms, fl, cap)
         if n < 0:
             raise RuntimeError("pt_prof_collect_list failed")
         return list(ms[:n]), list(fl[:n])
@@ -622,6 +613,5 @@ class Profiler:
     @staticmethod
     def collect(family: str):
         n, ms, fl = C.c_int64(), C.c_double(), C.c_double()
-        hip.check(hip.lib().pt_prof_collect(Profiler.FAMILIES[family], C.byref(n), C.byref(ms), C.byref(fl)),
-                  "pt_prof_collect")
+        hip.checked().pt_prof_collect(Profiler.FAMILIES[family], C.byref(n), C.byref(ms), C.byref(fl))
         return dict(launches=n.value, ms=ms.value, flops=fl.value)

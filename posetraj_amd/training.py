@@ -89,8 +89,8 @@ def _edm_loss(pred: torch.Tensor, noisy: torch.Tensor, target: torch.Tensor, sig
     if cl.dtype not in (torch.float16, torch.float32):
         cl = cl.float()
     out = torch.empty(B, dtype=torch.float32, device=pred.device)
-    hip.check(hip.lib().pt_edm_loss(cl.data_ptr(), 1 if cl.dtype == torch.float32 else 0, Cc, noisy.data_ptr(), target.data_ptr(),
-                                    sigmas.data_ptr(), B, F, h * w, out.data_ptr(), ops._stream()), "pt_edm_loss")
+    hip.checked().pt_edm_loss(cl.data_ptr(), 1 if cl.dtype == torch.float32 else 0, Cc, noisy.data_ptr(), target.data_ptr(),
+                              sigmas.data_ptr(), B, F, h * w, out.data_ptr(), ops._stream())
     return out
 
 
@@ -140,8 +140,8 @@ def _edm_train_input(I: dict) -> dict:
     lat, (B, F, h, w) = I["lat"], I["dims"]
     I["noisy"] = torch.empty_like(lat)
     I["x"] = torch.empty((B, F, h, w, 8), dtype=torch.float16, device=lat.device)
-    hip.check(hip.lib().pt_edm_train_input(lat.data_ptr(), I["noise"].data_ptr(), I["sig"].data_ptr(), I["cond_scale"].data_ptr(), TRAIN_NOISE_AUG,
-                                           B, F, h * w, I["noisy"].data_ptr(), I["x"].data_ptr(), ops._stream()), "pt_edm_train_input")
+    hip.checked().pt_edm_train_input(lat.data_ptr(), I["noise"].data_ptr(), I["sig"].data_ptr(), I["cond_scale"].data_ptr(), TRAIN_NOISE_AUG,
+                                     B, F, h * w, I["noisy"].data_ptr(), I["x"].data_ptr(), ops._stream())
     return I
 
 
@@ -391,7 +391,7 @@ class ControlNetTrainer:
         lat, noisy, sig, timesteps, ids = I["lat"], I["noisy"], I["sig"], I["timesteps"], I["ids"]
         ehs16 = I["ehs"].to(dtype=torch.float16).reshape(1, -1).contiguous()
         inp = I["x"].permute(0, 1, 4, 2, 3)
-        L = hip.lib()
+        L = hip.checked()
         # three tapes: the ControlNet's forward, the decoder pass of the temporal loss and the one-frame decoder pass of the spatial
         # loss.  The spatial pass is 1/14 of the work in ~1 500 launches over 180 ... 2 880 rows - latency, not throughput - and
         # depends on the temporal pass nowhere between the ControlNet's outputs and the join of the residual gradients: it runs on
@@ -420,11 +420,11 @@ class ControlNetTrainer:
 
         def loss_of(p: AD.Var, nz, tg, frames, weight):
             out = torch.empty(1, dtype=torch.float32, device=dev)
-            hip.check(L.pt_edm_loss(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
-                                    out.data_ptr(), ops._stream()), "pt_edm_loss")
+            L.pt_edm_loss(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
+                          out.data_ptr(), ops._stream())
             g = torch.empty((p.v.shape[0], 8), dtype=torch.float16, device=dev)
-            hip.check(L.pt_edm_loss_bwd(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
-                                        float(scale * weight), g.data_ptr(), ops._stream()), "pt_edm_loss_bwd")
+            L.pt_edm_loss_bwd(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
+                              float(scale * weight), g.data_ptr(), ops._stream())
             p.g = g
             return out
 
@@ -493,7 +493,7 @@ class ControlNetTrainer:
     def grad_norm(self) -> float:
         """Global L2 norm of the (un-scaled) gradients; ``inf`` / ``nan`` when an fp16 gradient overflowed."""
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        hip.check(hip.lib().pt_sumsq_f32(self.params.grad.data_ptr(), self.params.numel, acc.data_ptr(), ops._stream()), "pt_sumsq_f32")
+        hip.checked().pt_sumsq_f32(self.params.grad.data_ptr(), self.params.numel, acc.data_ptr(), ops._stream())
         return math.sqrt(float(acc)) / ((self._accum_scale or 1.0) * self.world) if math.isfinite(float(acc)) else float(acc)
 
     def optimizer_step(self, grad_norm: Optional[float] = None) -> bool:
@@ -516,9 +516,9 @@ class ControlNetTrainer:
             adamw = (P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel, self.last_lr, self.betas[0],
                      self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, 1.0 / (self._accum_scale * self.world), P.flat16.data_ptr(), 1)
             if ema is not None and self.ema_fused:        # ... and the EMA of the new parameters in the same pass
-                hip.check(hip.lib().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream()), "pt_adamw_ema_f32")
+                hip.checked().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream())
             else:
-                hip.check(hip.lib().pt_adamw_fused_f32(*adamw, ops._stream()), "pt_adamw_fused_f32")
+                hip.checked().pt_adamw_fused_f32(*adamw, ops._stream())
                 if ema is not None:
                     ema.update(omd)
             P.version += 1

@@ -67,8 +67,8 @@ class EMAModel:
     def update(self, one_minus_decay: float) -> None:
         """The device half on its own: ``shadow -= one_minus_decay * (shadow - params)`` over the flat buffers, current stream."""
         from . import hip, ops
-        hip.check(hip.lib().pt_ema_update_f32(self.shadow.data_ptr(), self.params.flat.data_ptr(), self.params.numel, one_minus_decay,
-                                              ops._stream()), "pt_ema_update_f32")
+        hip.checked().pt_ema_update_f32(self.shadow.data_ptr(), self.params.flat.data_ptr(), self.params.numel, one_minus_decay,
+                                        ops._stream())
 
     def step(self) -> None:
         """``ema.step(controlnet.parameters())`` as a launch of its own.  (A ``ControlNetTrainer(use_ema=True)`` steps its EMA inside

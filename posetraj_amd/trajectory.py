@@ -82,7 +82,7 @@ def trajectory_maps(tracks, size, original_size, num_frames: int = 14, mode: str
         pts, n_points, n_maps = torch.zeros((1, 2, 2), dtype=torch.int32, device=device), 2, 0
     H, W = int(size[0]), int(size[1])
     out = torch.empty((num_frames, 3, H, W), dtype=dtype, device=device)
-    hip.check(hip.lib().pt_rasterize_tracks(pts.data_ptr(), n_tracks, n_points, start if n_tracks else 0, n_maps, num_frames, H, W,
-                                            1 if mode == "dataset" else 0, 1 if dtype == torch.float32 else 0, out.data_ptr(),
-                                            ops._stream()), "pt_rasterize_tracks")
+    hip.checked().pt_rasterize_tracks(pts.data_ptr(), n_tracks, n_points, start if n_tracks else 0, n_maps, num_frames, H, W,
+                                      1 if mode == "dataset" else 0, 1 if dtype == torch.float32 else 0, out.data_ptr(),
+                                      ops._stream())
     return out

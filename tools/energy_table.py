@@ -146,7 +146,7 @@ def replay(calls, seconds, clock, label, repeat_each=1):
 def _replay(calls, seconds, clock, label, repeat_each=1):
     if not calls:
         return None
-    fns = [(getattr(hip._lib.real, n), [k[0] for k in kept]) for n, kept in calls for _ in range(repeat_each)]
+    fns = [(getattr(hip._checked.real, n), [k[0] for k in kept]) for n, kept in calls for _ in range(repeat_each)]
     for fn, args in fns:                                        # one warm pass
         fn(*args)
     torch.cuda.synchronize()
@@ -194,9 +194,9 @@ def main():
     clip = bench.synth_clip(H, W, 14, 1024, 1234, dev, sched.init_noise_sigma)
     pipe.denoise(*clip, num_inference_steps=2)                  # warm-up: packs, condition-encoder cache, allocator
     torch.cuda.synchronize()
-    hip.lib()
-    rec = Recorder(hip._lib)
-    hip._lib = rec
+    hip.checked()                                               # the handle the product calls through
+    rec = Recorder(hip._checked)
+    hip._checked = rec
     keep = []
     orig_ptr = torch.Tensor.data_ptr
 
