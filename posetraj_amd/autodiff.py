@@ -788,6 +788,7 @@ def _attention_backward(qkv: torch.Tensor, dout: torch.Tensor, Cc: int, heads: i
 
 ATTN_SCORE_BYTES = 2 << 30          # score-matrix memory (fp32) the recomputing attention backward holds at a time
 FLASH_BACKWARD = True               # spatial attention: pt_attn_fwd_lse_f16 / pt_attn_bwd_f16 (False: recompute through pt_gemm_f16)
+TEMPORAL_FLASH_FRAMES = 32          # temporal attention: clips up to this many frames take pt_attn_temporal_bwd_f16 (16: longer ones recompute)
 
 
 def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> Var:
@@ -813,6 +814,11 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
         dy, out.g = out.g, None
         if dy is None:
             return
+        if S == 1:                                   # one position (the mid block of an 8 x 8 latent): like one frame below, dV = dO and
+            dqkv = torch.zeros_like(qkv.v)           # dQ = dK = 0 EXACTLY (the kernels' dP - Dq cancels to rounding only: ~1e-7 of dP)
+            dqkv[:, 2 * Cc:].copy_(dy)
+            _acc(qkv, dqkv)
+            return
         if not flash:
             chunk = max(1, ATTN_SCORE_BYTES // (heads * S * S * 4))
             _acc(qkv, _attention_backward(qkv.v, dy, Cc, heads, hd, S, 1, (N, S, 1, 0), chunk))
@@ -829,7 +835,10 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
 
 
 def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: int) -> Var:
-    """Self-attention over the F frames of each spatial position; token f of (clip b, position s) is row (b F + f) S + s."""
+    """Self-attention over the F frames of each spatial position; token f of (clip b, position s) is row (b F + f) S + s.
+    Backward: one frame is the exact shortcut; up to ``TEMPORAL_FLASH_FRAMES`` frames (32, what the kernel covers: one block of 16
+    frames per wave, two above 16) at head sizes 64 / 128 the one-launch ``pt_attn_temporal_bwd_f16``; everything else recomputes
+    the scores through ``_attention_backward``."""
     Cc = heads * hd
     out = Var(ops.attn_temporal(qkv.v, B, F, S, heads, hd))
 
@@ -842,7 +851,7 @@ def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: 
             dqkv[:, 2 * Cc:].copy_(dy)
             _acc(qkv, dqkv)
             return
-        if FLASH_BACKWARD and F <= 16 and hd in (64, 128):
+        if FLASH_BACKWARD and F <= TEMPORAL_FLASH_FRAMES and hd in (64, 128):
             dqkv = torch.empty_like(qkv.v)
             hip.checked().pt_attn_temporal_bwd_f16(qkv.v.data_ptr(), qkv.v.stride(0), Cc, 2 * Cc, dy.data_ptr(), dy.stride(0), dqkv.data_ptr(),
                                                    dqkv.stride(0), B, F, S, heads, hd, hd ** -0.5, _stream())

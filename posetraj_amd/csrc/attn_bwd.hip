@@ -16,6 +16,9 @@
 //      dV^T[d][key] += dO^T P,   dK^T[d][key] += Q^T dS                 dO^T / Q^T by transposed reads of the staged tiles
 //
 // v_mfma_f32_16x16x32_f16 throughout; P and dS are fp16 operands (like the forward's P), sums fp32.  head_dim 64 / 128.
+//
+// The temporal attentions (F <= 32 frames of one spatial position) need neither passes nor a stored log-sum-exp: one wave holds
+// the whole F x F problem.  attn_temporal_bwd_kernel: F <= 16 (one block of 16 frames); attn_temporal_bwd2_kernel: 17 .. 32 (two).
 #include "pt_common.h"
 
 namespace {
@@ -402,6 +405,171 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_kernel(const f16* __res
     }
 }
 
+// The same for 17 <= F <= 32 frames (SVD-XT: 25): two blocks of 16 frames, as pt_attn_temporal_f16's NB = 2.  Lane (c, g) loads
+// the fragments of frames c and 16 + c (frames >= F read as zero) and stages Q / K / dO as [32][HDIM] rows (padded pitch, like
+// the spatial passes above).  Scores per (query block qb, key block kb) in both orientations: 16 accumulators; orientation a
+// reduces over the key = the two kb accumulators in-lane and the 16 lanes of a row group, orientation b over the four in-lane
+// rows, the two kb accumulators and xor 16 / 32.  Same rounding points as the one-block kernel (P and dS to fp16 once).  The
+// products over the frames are ONE v_mfma_f32_16x16x32_f16 each: P / dS of the two blocks of the summed frame index are the
+// two halves of the B operand, and the A operand is two transposed reads (ds_read_b64_tr_b16) of the staged rows, 16 frames
+// apart - the operand pairing of attn_bwd_dkv_kernel.  HDIM = 128 runs two waves per workgroup (LDS: 54 KB; 60 KB for four at 64).
+template <int HDIM, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void attn_temporal_bwd2_kernel(const f16* __restrict__ qkv, int ld, int k_off, int v_off,
+                                                                        const f16* __restrict__ dout, int ldo, f16* __restrict__ dqkv, int ldd, int F,
+                                                                        int S, int heads, int64_t ntasks, float scale) {
+    constexpr int NS = HDIM / 32;
+    constexpr int PITCH = 2 * HDIM + 32;                                  // bytes per staged row
+    __shared__ __attribute__((aligned(16))) char smem[WAVES * 3 * 32 * PITCH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t task = (int64_t)blockIdx.x * WAVES + wave;
+    if (task >= ntasks) return;
+    const int head = (int)(task % heads);
+    const int64_t bs = task / heads;
+    const int s = (int)(bs % S);
+    const int64_t b = bs / S;
+    const int c = lane & 15, g = lane >> 4;
+    char* const Qs = smem + wave * (3 * 32 * PITCH);
+    char* const Ks = Qs + 32 * PITCH;
+    char* const Os = Ks + 32 * PITCH;
+    const f16x8 zero8 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+    bool live[2];                                                         // frame 16 blk + c (this lane's fragment row / output column) exists
+    int64_t row[2];
+    f16x8 qf[2][NS], kf[2][NS], vf[2][NS], of[2][NS];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+        live[blk] = 16 * blk + c < F;
+        row[blk] = (b * F + (live[blk] ? 16 * blk + c : 0)) * (int64_t)S + s;
+        const f16* rp = qkv + row[blk] * ld + head * HDIM + g * 8;
+        const f16* op = dout + row[blk] * ldo + head * HDIM + g * 8;
+#pragma unroll
+        for (int h = 0; h < NS; ++h) {
+            qf[blk][h] = live[blk] ? *(const f16x8*)(rp + 32 * h) : zero8;
+            kf[blk][h] = live[blk] ? *(const f16x8*)(rp + k_off + 32 * h) : zero8;
+            vf[blk][h] = live[blk] ? *(const f16x8*)(rp + v_off + 32 * h) : zero8;
+            of[blk][h] = live[blk] ? *(const f16x8*)(op + 32 * h) : zero8;
+        }
+    }
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+        for (int h = 0; h < NS; ++h) {
+            const int at = (16 * blk + c) * PITCH + 64 * h + 16 * g;
+            *(f16x8*)(Qs + at) = qf[blk][h];
+            *(f16x8*)(Ks + at) = kf[blk][h];
+            *(f16x8*)(Os + at) = of[blk][h];
+        }
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    // ---- orientation a: rows q = 16 qb + 4 g + i, column k = 16 kb + c; softmax over the keys = (kb, the 16 lanes of a row group)
+    f16x8 pa[2], dsa[2];                                                  // [kb]: element 4 qb + i
+    {
+        f32x4 sa[2][2], da[2][2];                                         // [qb][kb]
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                sa[qb][kb] = z4;
+                da[qb][kb] = z4;
+#pragma unroll
+                for (int h = 0; h < NS; ++h) {
+                    sa[qb][kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[qb][h], kf[kb][h], sa[qb][kb], 0, 0, 0);
+                    da[qb][kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(of[qb][h], vf[kb][h], da[qb][kb], 0, 0, 0);
+                }
+            }
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float v[2], m = -INFINITY;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) { v[kb] = live[kb] ? sa[qb][kb][i] * scale : -INFINITY; m = fmaxf(m, v[kb]); }
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+                float e[2], z = 0.f;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) { e[kb] = live[kb] ? __expf(v[kb] - m) : 0.f; z += e[kb]; }
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) z += __shfl_xor(z, o);
+                const bool qlive = 16 * qb + 4 * g + i < F;
+                float dd = 0.f;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) { e[kb] = qlive ? e[kb] / z : 0.f; dd += e[kb] * da[qb][kb][i]; }
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) dd += __shfl_xor(dd, o);
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+                    pa[kb][4 * qb + i] = (f16)e[kb];
+                    dsa[kb][4 * qb + i] = (f16)(e[kb] * (da[qb][kb][i] - dd) * scale);
+                }
+            }
+    }
+    // ---- orientation b: rows k = 16 kb + 4 g + i, column q = 16 qb + c; softmax over the keys = (kb, in-lane i, the four row groups)
+    f16x8 dsb[2];                                                         // [qb]: element 4 kb + i
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        f32x4 sb[2], db[2];                                               // [kb]
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            sb[kb] = z4;
+            db[kb] = z4;
+#pragma unroll
+            for (int h = 0; h < NS; ++h) {
+                sb[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kb][h], qf[qb][h], sb[kb], 0, 0, 0);
+                db[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[kb][h], of[qb][h], db[kb], 0, 0, 0);
+            }
+        }
+        float v[2][4], m = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { v[kb][i] = (16 * kb + 4 * g + i < F) ? sb[kb][i] * scale : -INFINITY; m = fmaxf(m, v[kb][i]); }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        float e[2][4], z = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { e[kb][i] = (16 * kb + 4 * g + i < F) ? __expf(v[kb][i] - m) : 0.f; z += e[kb][i]; }
+        z += __shfl_xor(z, 16);
+        z += __shfl_xor(z, 32);
+        float dd = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { e[kb][i] = live[qb] ? e[kb][i] / z : 0.f; dd += e[kb][i] * db[kb][i]; }
+        dd += __shfl_xor(dd, 16);
+        dd += __shfl_xor(dd, 32);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dsb[qb][4 * kb + i] = (f16)(e[kb][i] * (db[kb][i] - dd) * scale);
+    }
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                            // this wave's staged rows are in LDS
+    __builtin_amdgcn_wave_barrier();
+    // transposed fragments: element j of lane (c, g) = staged row 4 g + j (second read: 16 + 4 g + j), column 16 blk + c
+    const int tr = (4 * g + (c >> 2)) * PITCH + 8 * (c & 3);
+#pragma unroll
+    for (int blk = 0; blk < HDIM / 16; ++blk) {
+        const f16x4 olo = pt_lds_tr16(Os + tr + 32 * blk), ohi = pt_lds_tr16(Os + tr + 16 * PITCH + 32 * blk);
+        const f16x4 qlo = pt_lds_tr16(Qs + tr + 32 * blk), qhi = pt_lds_tr16(Qs + tr + 16 * PITCH + 32 * blk);
+        const f16x4 klo = pt_lds_tr16(Ks + tr + 32 * blk), khi = pt_lds_tr16(Ks + tr + 16 * PITCH + 32 * blk);
+        const f16x8 ot = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
+        const f16x8 qt = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
+        const f16x8 kt = {klo[0], klo[1], klo[2], klo[3], khi[0], khi[1], khi[2], khi[3]};
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb) {                                  // output column c = frame 16 fb + c; rows d = 16 blk + 4 g + i
+            const f32x4 dv = __builtin_amdgcn_mfma_f32_16x16x32_f16(ot, pa[fb], z4, 0, 0, 0);     // dV^T[d][k] = sum_q dO^T[d][q] P[q][k]
+            const f32x4 dk = __builtin_amdgcn_mfma_f32_16x16x32_f16(qt, dsa[fb], z4, 0, 0, 0);    // dK^T[d][k] = sum_q Q^T[d][q] dS[q][k]
+            const f32x4 dq = __builtin_amdgcn_mfma_f32_16x16x32_f16(kt, dsb[fb], z4, 0, 0, 0);    // dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]
+            if (live[fb]) {
+                f16* const gq = dqkv + row[fb] * ldd + head * HDIM + 4 * g + 16 * blk;
+                *(f16x4*)gq = (f16x4){(f16)dq[0], (f16)dq[1], (f16)dq[2], (f16)dq[3]};
+                *(f16x4*)(gq + k_off) = (f16x4){(f16)dk[0], (f16)dk[1], (f16)dk[2], (f16)dk[3]};
+                *(f16x4*)(gq + v_off) = (f16x4){(f16)dv[0], (f16)dv[1], (f16)dv[2], (f16)dv[3]};
+            }
+        }
+    }
+}
+
 template <int D>
 int launch_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldout, const void* dout, int ldo,
                const float* lse, float* dq_dot, void* dq, void* dk, void* dv, int ldd, int nbatch, int S, int heads, float scale, hipStream_t s) {
@@ -455,20 +623,21 @@ extern "C" int pt_attn_temporal_bwd_f16(const void* qkv, int32_t ld, int32_t k_o
                                         int32_t ldd, int32_t B, int32_t F, int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream) {
     PT_CHECK(qkv && dout && dqkv, "pt_attn_temporal_bwd_f16: null pointer");
     PT_CHECK(head_dim == 64 || head_dim == 128, "pt_attn_temporal_bwd_f16: head_dim %d unsupported (64, 128)", head_dim);
-    PT_CHECK(F > 0 && F <= 16, "pt_attn_temporal_bwd_f16: %d frames (at most 16; longer clips go through pt_gemm_f16)", F);
+    PT_CHECK(F >= 1 && F <= 32, "pt_attn_temporal_bwd_f16: %d frames unsupported (1..32)", F);
     PT_CHECK(ld % 8 == 0 && ldo % 8 == 0 && ldd % 4 == 0 && k_off % 8 == 0 && v_off % 8 == 0, "pt_attn_temporal_bwd_f16: pitches / offsets must be multiples of 8 (gradient pitch: 4)");
     PT_CHECK((((uintptr_t)qkv | (uintptr_t)dout) & 15) == 0 && ((uintptr_t)dqkv & 7) == 0, "pt_attn_temporal_bwd_f16: misaligned pointer");
     PT_CHECK(B > 0 && S > 0 && heads > 0 && scale > 0.f, "pt_attn_temporal_bwd_f16: bad sizes");
     const int64_t ntasks = (int64_t)B * S * heads;
-    const int64_t blocks = (ntasks + 3) / 4;
+    const int waves = (F > 16 && head_dim == 128) ? 2 : 4;                // waves (tasks) per workgroup
+    const int64_t blocks = (ntasks + waves - 1) / waves;
     PT_CHECK(blocks < (1ll << 31), "pt_attn_temporal_bwd_f16: grid too large");
     hipStream_t s = (hipStream_t)stream;
-    if (head_dim == 64)
-        hipLaunchKernelGGL(attn_temporal_bwd_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, s, (const f16*)qkv, ld, k_off, v_off, (const f16*)dout, ldo,
-                           (f16*)dqkv, ldd, F, S, heads, ntasks, scale);
-    else
-        hipLaunchKernelGGL(attn_temporal_bwd_kernel<128>, dim3((unsigned)blocks), dim3(256), 0, s, (const f16*)qkv, ld, k_off, v_off, (const f16*)dout, ldo,
-                           (f16*)dqkv, ldd, F, S, heads, ntasks, scale);
+#define PT_TBWD(KERNEL_)                                                                                                                    \
+    hipLaunchKernelGGL((KERNEL_), dim3((unsigned)blocks), dim3(64 * waves), 0, s, (const f16*)qkv, ld, k_off, v_off, (const f16*)dout, ldo, \
+                       (f16*)dqkv, ldd, F, S, heads, ntasks, scale)
+    if (head_dim == 64) { if (F <= 16) PT_TBWD(attn_temporal_bwd_kernel<64>); else PT_TBWD((attn_temporal_bwd2_kernel<64, 4>)); }
+    else                { if (F <= 16) PT_TBWD(attn_temporal_bwd_kernel<128>); else PT_TBWD((attn_temporal_bwd2_kernel<128, 2>)); }
+#undef PT_TBWD
     PT_LAUNCH_CHECK("pt_attn_temporal_bwd_f16");
     return 0;
 }

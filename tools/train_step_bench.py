@@ -5,6 +5,7 @@ of the three families (pt_igemm_f16: forward and data gradients; pt_gemm_f16: we
 the memory high-water mark.
 
     python tools/train_step_bench.py [--steps 5] [--height 320 --width 576] [--frames 14] [--tiny] [--gemm-table] [--igemm-table]
+        [--temporal-bwd fused|recompute]
     python tools/train_step_bench.py --json --steps 7 --warmup 3      # what bench.py --train-step runs as a child process:
         wall-clock median without hipEvent brackets, the host's enqueue time, full garbage collections inside the timed steps
 """
@@ -35,11 +36,16 @@ def main():
     ap.add_argument("--no-wgrad-stream", action="store_true"); ap.add_argument("--no-encoder-stream", action="store_true"); ap.add_argument("--no-spatial-stream", action="store_true"); ap.add_argument("--no-pack-stream", action="store_true")
     ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off",
                     help="ControlNetTrainer(use_ema=True): the EMA inside the AdamW launch (pt_adamw_ema_f32) or as pt_ema_update_f32 behind pt_adamw_fused_f32")
+    ap.add_argument("--temporal-bwd", choices=("fused", "recompute"), default="fused",
+                    help="temporal attention backward of clips of 17 - 32 frames: pt_attn_temporal_bwd_f16 (autodiff.TEMPORAL_FLASH_FRAMES = 32) or the "
+                         "recomputing path through pt_gemm_f16 (16)")
     ap.add_argument("--json", action="store_true", help="bench.py's train_step leg: time the steps without hipEvent brackets (median), count the matrix "
                                                       "flops in one extra bracketed step, print ONE JSON object")
     a = ap.parse_args()
     from posetraj_amd import ControlNetSDVModel, UNetSpatioTemporalConditionControlNetModel, hip
+    from posetraj_amd import autodiff
     from posetraj_amd.training import ControlNetTrainer
+    autodiff.TEMPORAL_FLASH_FRAMES = 32 if a.temporal_bwd == "fused" else 16
     dev = torch.device("cuda:0")
     cfg = dict(num_attention_heads=(5, 10, 20, 20), num_frames=a.frames)
     ce = (16, 32, 96, 256)
