@@ -141,7 +141,9 @@ class ParamStore:
     reads whole rows.  ``value()`` / ``gradient()`` return views in torch's shape (permuted strides), so callers never see it;
     AdamW is element-wise and does not care."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], device):
+    def __init__(self, sd: Dict[str, torch.Tensor], device, use_8bit_adam: bool = False):
+        """``use_8bit_adam``: no full-size moment buffers (``exp_avg`` / ``exp_avg_sq`` are None); ``adam8`` holds the block-quantised
+        state instead (``training_utils.Adam8bitState``)."""
         self.names = list(sd)
         self.offsets, n = {}, 0
         for k in self.names:
@@ -150,9 +152,13 @@ class ParamStore:
         self.numel = n
         self.flat = torch.zeros(n, dtype=torch.float32, device=device)
         self.grad = torch.zeros(n, dtype=torch.float32, device=device)
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
+        self.exp_avg = None if use_8bit_adam else torch.zeros(n, dtype=torch.float32, device=device)
+        self.exp_avg_sq = None if use_8bit_adam else torch.zeros(n, dtype=torch.float32, device=device)
         self.shapes = {k: tuple(sd[k].shape) for k in self.names}
+        self.adam8 = None
+        if use_8bit_adam:
+            from .training_utils import Adam8bitState
+            self.adam8 = Adam8bitState(self)
         for k in self.names:
             self.value(k).copy_(sd[k].to(device=device, dtype=torch.float32))
         self.version, self.trainable = 0, True
@@ -224,9 +230,12 @@ class ParamStore:
         return T, shape[0], shape[1]
 
     def _view(self, buf, k):
+        return self.shaped(self.raw(buf, k), k)
+
+    def shaped(self, flat, k):
+        """A parameter's stored elements (``raw`` of a flat buffer, or a compact copy of them) as a view in torch's shape."""
         shape = self.shapes[k]
         lay = self.layout(k)
-        flat = self.raw(buf, k)
         if lay is None or lay[0] == 1:
             return flat.view(shape)
         T, Co, Ci = lay

@@ -4,6 +4,7 @@
 // HBM-bound passes over channels-last fp16 activations with fp32 statistics; parameter gradients are ACCUMULATED into fp32
 // buffers with atomics (the caller zeroes them once per optimizer step, so gradient accumulation over micro-batches is free).
 #include "pt_common.h"
+#include "../../include/posetraj_optim.h"
 
 namespace {
 
@@ -673,6 +674,22 @@ __device__ __forceinline__ float ema_update(float s, float p, float omd) {
     return s - t;
 }
 
+// AdamW's statements for one element (those of adamw_kernel): p, m, v in and out, g un-scaled on the way in.  One copy for the fused
+// kernel and the 8-bit one, and every multiply-add spelled out under `fp contract(off)`: left to the compiler, WHICH product of
+// `c p - k q` or `b1 m + (1 - b1) g` joins the addition in a v_fma depends on the code around the statement, and the two kernels
+// then differ in the last bit.  The roundings below are the ones the fused kernel has always had.
+struct AdamwScalars { float lr, b1, b2, eps, wd, bc1, bc2_sqrt, inv_scale; };
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwScalars& a) {
+#pragma clang fp contract(off)
+    const float gi = g * a.inv_scale;
+    const float mi = __builtin_fmaf(a.b1, m, (1.0f - a.b1) * gi);
+    const float vi = __builtin_fmaf(a.b2, v, (1.0f - a.b2) * gi * gi);
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / a.bc2_sqrt + a.eps;
+    const float step = -(a.lr / a.bc1) * (mi / denom);           // (the sign rides on the uniform factor: no negation per element)
+    p = __builtin_fmaf(__builtin_fmaf(-a.lr, a.wd, 1.0f), p, step);
+}
+
 // EMA = true: the shadow follows the NEW parameter while it is still in a register (one more read and one more write of a buffer whose
 // neighbours are already here: 8 bytes per parameter on top of 34, against 12 for a launch of its own).
 template <bool EMA>
@@ -680,6 +697,7 @@ __global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p,
                                                           int64_t n4, float lr, float b1, float b2, float eps, float wd, float bc1,
                                                           float bc2_sqrt, float inv_scale, f16* __restrict__ mirror, int zero_g,
                                                           float* __restrict__ shadow, float omd) {
+    const AdamwScalars a = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, inv_scale};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const f32x4 g4 = *(const f32x4*)(g + 4 * i), m4 = *(const f32x4*)(m + 4 * i), v4 = *(const f32x4*)(v + 4 * i);
         f32x4 p4 = *(const f32x4*)(p + 4 * i), mo, vo, s4;
@@ -687,13 +705,9 @@ __global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p,
         if constexpr (EMA) s4 = *(const f32x4*)(shadow + 4 * i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gi = g4[j] * inv_scale;
-            float pi = p4[j] * (1.0f - lr * wd);
-            const float mi = b1 * m4[j] + (1.0f - b1) * gi;
-            const float vi = b2 * v4[j] + (1.0f - b2) * gi * gi;
+            float pi = p4[j], mi = m4[j], vi = v4[j];
+            adamw_one(pi, g4[j], mi, vi, a);
             mo[j] = mi; vo[j] = vi;
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            pi -= (lr / bc1) * (mi / denom);
             p4[j] = pi;
             h4[j] = (f16)pi;
             if constexpr (EMA) s4[j] = ema_update(s4[j], pi, omd);
@@ -713,6 +727,165 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ sha
 #pragma unroll
         for (int j = 0; j < 4; ++j) s4[j] = ema_update(s4[j], p4[j], omd);
         *(f32x4*)(shadow + 4 * i) = s4;
+    }
+}
+
+// ---- --use_8bit_adam (round 8): AdamW over block-quantised moments (include/posetraj_optim.h: pto_adamw8_f32) -------------
+// The store is cut into UNITS of 256 elements that never cross a parameter (pt_adam8_segment.work counts them); one wave takes one
+// unit at a time, 4 elements per lane (16-byte loads of p and g, 4 bytes of codes), and every wave owns a contiguous run of units:
+// it looks its first unit's parameter up once (binary search over the table's `work` column) and then walks the table forward.
+// Everything that places a unit is wave-uniform.  A unit is checked against the buffers' extents before anything is touched.
+constexpr int ADAM8_BLOCK = 256;
+
+struct Adam8Unit {
+    int64_t e0;          // first element of the unit in p
+    int64_t st;          // kind 1: its block; kind 0: offset of its first fp32 moment
+    int len, kind;       // elements (1 .. 256)
+};
+
+struct Adam8Walk {
+    const pt_adam8_segment* seg;
+    int nseg, s;
+    int64_t n, n_blocks, n_f32;
+    __device__ __forceinline__ void seek(int64_t w) {           // the last entry whose `work` is <= w
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((int64_t)seg[mid].work <= w) lo = mid; else hi = mid - 1;
+        }
+        s = lo;
+    }
+    // unit w (not below the last one asked for); false: the table is inconsistent with the buffers there, nothing may be touched
+    __device__ __forceinline__ bool unit(int64_t w, Adam8Unit& u) {
+        while (s + 1 < nseg && (int64_t)seg[s + 1].work <= w) ++s;
+        const pt_adam8_segment e = seg[s];
+        const int64_t local = w - e.work, first = local * ADAM8_BLOCK, left = e.count - first;
+        u.e0 = e.start + first;
+        u.len = (int)(left < ADAM8_BLOCK ? left : ADAM8_BLOCK);
+        u.kind = e.kind;
+        u.st = e.kind ? e.state + local : e.state + first;
+        const int64_t len4 = (u.len + 3) & ~3;
+        bool ok = local >= 0 && left > 0 && e.start >= 0 && (e.start & 3) == 0 && u.e0 + len4 <= n && e.state >= 0;
+        ok = ok && (e.kind ? u.st < n_blocks : ((e.state & 3) == 0 && u.st + len4 <= n_f32));
+        return ok;
+    }
+};
+
+// largest i with book[i] <= x (0 if there is none), then the nearer of book[i] and book[i + 1]; a tie keeps the lower.  book: 256
+// ascending floats in LDS - 9 dependent ds_read_b32 per value
+__device__ __forceinline__ int adam8_nearest(const float* book, float x) {
+    int lo = 0;
+    float below = book[0];
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        const float t = book[lo + s];
+        if (t <= x) { lo += s; below = t; }
+    }
+    const int up = lo < 255 ? lo + 1 : 255;
+    return (x - below > book[up] - x) ? up : lo;
+}
+
+__device__ __forceinline__ float adam8_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw8_kernel(float* __restrict__ p, float* __restrict__ g, uint8_t* __restrict__ c1, uint8_t* __restrict__ c2,
+                                                     float* __restrict__ am1, float* __restrict__ am2, const float* __restrict__ q1,
+                                                     const float* __restrict__ q2, float* __restrict__ m32, float* __restrict__ v32,
+                                                     Adam8Walk walk, int64_t n_work, int64_t per_wave, AdamwScalars a, f16* __restrict__ mirror,
+                                                     int zero_g, float* __restrict__ shadow, float omd) {
+    __shared__ float book1[256], book2[256];
+    book1[threadIdx.x] = q1[threadIdx.x];
+    book2[threadIdx.x] = q2[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int64_t w0 = wave * per_wave, w1 = w0 + per_wave < n_work ? w0 + per_wave : n_work;
+    if (w0 >= w1) return;
+    walk.seek(w0);
+    for (int64_t w = w0; w < w1; ++w) {
+        Adam8Unit u;
+        if (!walk.unit(w, u)) continue;
+        const bool on = 4 * lane < u.len;                       // this lane's four elements hold at least one of the unit's
+        const int64_t e = u.e0 + 4 * lane;
+        f32x4 p4 = {0.f, 0.f, 0.f, 0.f}, g4 = p4, m4 = p4, v4 = p4, s4 = p4;
+        uint32_t k1 = 0, k2 = 0;
+        if (on) {
+            p4 = *(const f32x4*)(p + e); g4 = *(const f32x4*)(g + e);
+            if constexpr (EMA) s4 = *(const f32x4*)(shadow + e);
+        }
+        if (u.kind) {
+            const float a1 = am1[u.st], a2 = am2[u.st];
+            if (on) {
+                k1 = *(const uint32_t*)(c1 + u.st * ADAM8_BLOCK + 4 * lane); k2 = *(const uint32_t*)(c2 + u.st * ADAM8_BLOCK + 4 * lane);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { m4[j] = book1[(k1 >> (8 * j)) & 255] * a1; v4[j] = book2[(k2 >> (8 * j)) & 255] * a2; }
+            }
+        } else if (on) {
+            m4 = *(const f32x4*)(m32 + u.st + 4 * lane); v4 = *(const f32x4*)(v32 + u.st + 4 * lane);
+        }
+        f32x4 po = p4, so = s4;
+        f16x4 h4;
+        float mx1 = 0.f, mx2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pi = p4[j], mi = m4[j], vi = v4[j];
+            adamw_one(pi, g4[j], mi, vi, a);
+            const bool live = 4 * lane + j < u.len;             // an element past the parameter's end keeps its value everywhere
+            if (live) { po[j] = pi; if constexpr (EMA) so[j] = ema_update(s4[j], pi, omd); }
+            m4[j] = live ? mi : 0.f; v4[j] = live ? vi : 0.f;
+            h4[j] = (f16)po[j];
+            mx1 = fmaxf(mx1, fabsf(m4[j])); mx2 = fmaxf(mx2, v4[j]);
+        }
+        if (u.kind) {
+            mx1 = adam8_wave_max(mx1); mx2 = adam8_wave_max(mx2);
+            if (on) {
+                k1 = k2 = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                   // absmax' == 0: every m (v) of the block is 0 - no division, the code of 0.0
+                    k1 |= (uint32_t)adam8_nearest(book1, mx1 > 0.f ? m4[j] / mx1 : 0.f) << (8 * j);
+                    k2 |= (uint32_t)adam8_nearest(book2, mx2 > 0.f ? v4[j] / mx2 : 0.f) << (8 * j);
+                }
+                *(uint32_t*)(c1 + u.st * ADAM8_BLOCK + 4 * lane) = k1; *(uint32_t*)(c2 + u.st * ADAM8_BLOCK + 4 * lane) = k2;
+            }
+            if (lane == 0) { am1[u.st] = mx1; am2[u.st] = mx2; }
+        } else if (on) {
+            *(f32x4*)(m32 + u.st + 4 * lane) = m4; *(f32x4*)(v32 + u.st + 4 * lane) = v4;
+        }
+        if (on) {
+            *(f32x4*)(p + e) = po;
+            if (mirror) *(f16x4*)(mirror + e) = h4;
+            if (zero_g) *(f32x4*)(g + e) = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (EMA) *(f32x4*)(shadow + e) = so;
+        }
+    }
+}
+
+// the 8-bit state as fp32 moments in the layout of p: book[code] * absmax (kind 1), a copy (kind 0)
+__global__ __launch_bounds__(256) void adam8_dequant_kernel(const uint8_t* __restrict__ c1, const uint8_t* __restrict__ c2, const float* __restrict__ am1,
+                                                            const float* __restrict__ am2, const float* __restrict__ q1, const float* __restrict__ q2,
+                                                            const float* __restrict__ m32, const float* __restrict__ v32, Adam8Walk walk,
+                                                            int64_t n_work, int64_t per_wave, float* __restrict__ m, float* __restrict__ v) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int64_t w0 = wave * per_wave, w1 = w0 + per_wave < n_work ? w0 + per_wave : n_work;
+    if (w0 >= w1) return;
+    walk.seek(w0);
+    for (int64_t w = w0; w < w1; ++w) {
+        Adam8Unit u;
+        if (!walk.unit(w, u)) continue;
+        for (int i = lane; i < u.len; i += 64) {
+            if (u.kind) {
+                m[u.e0 + i] = q1[c1[u.st * ADAM8_BLOCK + i]] * am1[u.st];
+                v[u.e0 + i] = q2[c2[u.st * ADAM8_BLOCK + i]] * am2[u.st];
+            } else {
+                m[u.e0 + i] = m32[u.st + i];
+                v[u.e0 + i] = v32[u.st + i];
+            }
+        }
     }
 }
 
@@ -1054,6 +1227,67 @@ extern "C" int pt_ema_update_f32(float* shadow, const float* p, int64_t n, float
     PT_CHECK(((uintptr_t)shadow & 15) == 0 && ((uintptr_t)p & 15) == 0, "pt_ema_update_f32: buffers must be 16-byte aligned");
     hipLaunchKernelGGL(ema_update_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n / 4, one_minus_decay);
     PT_LAUNCH_CHECK("pt_ema_update_f32");
+    return 0;
+}
+
+// the grid of the two 8-bit kernels: waves that each own `per_wave` consecutive units - at most 8 workgroups of 4 waves per CU
+static unsigned adam8_grid(int64_t n_work, int64_t* per_wave) {
+    const int64_t max_waves = 256 * 8 * 4;
+    *per_wave = (n_work + max_waves - 1) / max_waves;
+    const int64_t waves = (n_work + *per_wave - 1) / *per_wave;
+    return (unsigned)((waves + 3) / 4);
+}
+
+extern "C" int pto_abi_version(void) { return PT_OPTIM_ABI_VERSION; }
+
+extern "C" int pto_adamw8_f32(float* p, float* g, void* state1, void* state2, float* absmax1, float* absmax2, const float* qmap1, const float* qmap2,
+                             float* exp_avg_f32, float* exp_avg_sq_f32, const pt_adam8_segment* segments, int32_t n_segments, int64_t n_work,
+                             int64_t n, int64_t n_blocks, int64_t n_f32, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int32_t step, float inv_scale, void* half_mirror, int32_t zero_grad, float* ema_shadow, float one_minus_decay,
+                             void* stream) {
+    PT_CHECK(p && g && segments && n_segments > 0 && n_work > 0 && n > 0 && n % 4 == 0 && step >= 1, "pto_adamw8_f32: bad arguments (n must be a multiple of 4)");
+    PT_CHECK(qmap1 && qmap2, "pto_adamw8_f32: qmap1 / qmap2 (the two code books of 256 floats) must not be null");
+    PT_CHECK(n_blocks >= 0 && n_f32 >= 0 && n_f32 % 4 == 0 && n_work < ((int64_t)1 << 31), "pto_adamw8_f32: bad state extents (n_f32 must be a multiple of 4)");
+    PT_CHECK(n_blocks == 0 || (state1 && state2 && absmax1 && absmax2), "pto_adamw8_f32: n_blocks > 0 needs state1, state2, absmax1, absmax2");
+    PT_CHECK(n_f32 == 0 || (exp_avg_f32 && exp_avg_sq_f32), "pto_adamw8_f32: n_f32 > 0 needs exp_avg_f32, exp_avg_sq_f32");
+    PT_CHECK(ema_shadow != p, "pto_adamw8_f32: ema_shadow must be a buffer of its own");
+    auto al = [](const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; };
+    PT_CHECK(al(p, 16) && al(g, 16) && al(ema_shadow, 16) && al(exp_avg_f32, 16) && al(exp_avg_sq_f32, 16) && al(half_mirror, 8) && al(segments, 8) &&
+                 al(state1, 4) && al(state2, 4) && al(absmax1, 4) && al(absmax2, 4) && al(qmap1, 4) && al(qmap2, 4),
+             "pto_adamw8_f32: buffers must be aligned (p, g, ema_shadow, fp32 moments: 16 bytes; half_mirror, segments: 8; the rest: 4)");
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const AdamwScalars a = {lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), inv_scale};
+    const Adam8Walk walk = {segments, n_segments, 0, n, n_blocks, n_f32};
+    int64_t per_wave;
+    const unsigned blocks = adam8_grid(n_work, &per_wave);
+    if (ema_shadow)
+        hipLaunchKernelGGL(adamw8_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, (uint8_t*)state1, (uint8_t*)state2, absmax1, absmax2,
+                           qmap1, qmap2, exp_avg_f32, exp_avg_sq_f32, walk, n_work, per_wave, a, (f16*)half_mirror, zero_grad, ema_shadow, one_minus_decay);
+    else
+        hipLaunchKernelGGL(adamw8_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, (uint8_t*)state1, (uint8_t*)state2, absmax1, absmax2,
+                           qmap1, qmap2, exp_avg_f32, exp_avg_sq_f32, walk, n_work, per_wave, a, (f16*)half_mirror, zero_grad, (float*)nullptr, 0.0f);
+    PT_LAUNCH_CHECK("pto_adamw8_f32");
+    return 0;
+}
+
+extern "C" int pto_adam8_dequant_f32(const void* state1, const void* state2, const float* absmax1, const float* absmax2, const float* qmap1,
+                                    const float* qmap2, const float* exp_avg_f32, const float* exp_avg_sq_f32, const pt_adam8_segment* segments,
+                                    int32_t n_segments, int64_t n_work, int64_t n, int64_t n_blocks, int64_t n_f32, float* exp_avg, float* exp_avg_sq,
+                                    void* stream) {
+    PT_CHECK(exp_avg && exp_avg_sq && segments && n_segments > 0 && n_work > 0 && n > 0, "pto_adam8_dequant_f32: bad arguments");
+    PT_CHECK(qmap1 && qmap2, "pto_adam8_dequant_f32: qmap1 / qmap2 (the two code books of 256 floats) must not be null");
+    PT_CHECK(n_blocks >= 0 && n_f32 >= 0 && n_work < ((int64_t)1 << 31), "pto_adam8_dequant_f32: bad state extents");
+    PT_CHECK(n_blocks == 0 || (state1 && state2 && absmax1 && absmax2), "pto_adam8_dequant_f32: n_blocks > 0 needs state1, state2, absmax1, absmax2");
+    PT_CHECK(n_f32 == 0 || (exp_avg_f32 && exp_avg_sq_f32), "pto_adam8_dequant_f32: n_f32 > 0 needs exp_avg_f32, exp_avg_sq_f32");
+    PT_CHECK(((uintptr_t)segments & 7) == 0 && (((uintptr_t)absmax1 | (uintptr_t)absmax2 | (uintptr_t)qmap1 | (uintptr_t)qmap2 | (uintptr_t)exp_avg_f32 |
+                                                 (uintptr_t)exp_avg_sq_f32 | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 3) == 0,
+             "pto_adam8_dequant_f32: buffers must be aligned (segments: 8 bytes; floats: 4)");
+    const Adam8Walk walk = {segments, n_segments, 0, n, n_blocks, n_f32};
+    int64_t per_wave;
+    const unsigned blocks = adam8_grid(n_work, &per_wave);
+    hipLaunchKernelGGL(adam8_dequant_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)state1, (const uint8_t*)state2, absmax1,
+                       absmax2, qmap1, qmap2, exp_avg_f32, exp_avg_sq_f32, walk, n_work, per_wave, exp_avg, exp_avg_sq);
+    PT_LAUNCH_CHECK("pto_adam8_dequant_f32");
     return 0;
 }
 

@@ -18,6 +18,9 @@ HEADERS = ["pt_common.h", "igemm_tail.h"]
 HEADER = os.path.join(HERE, "..", "include", "posetraj_hip.h")
 STRUCT_CLASSES = {"pt_igemm_params": "IgemmParams", "pt_ffn_params": "FfnParams", "pt_lnlin_params": "LnLinParams",
                   "pt_conv_f32_params": "ConvF32Params", "pt_gemm_params": "GemmParams"}
+# the optimizer extension (include/posetraj_optim.h: entry points `pto_*` of the same library, a version of its own)
+OPTIM_HEADER = os.path.join(HERE, "..", "include", "posetraj_optim.h")
+OPTIM_STRUCT_CLASSES = {"pt_adam8_segment": "Adam8Segment"}
 
 _lib = _checked = None
 
@@ -28,7 +31,7 @@ _lib = _checked = None
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _TYPE = r"(?:const\s+)?\w+\s*\*?"
 _DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
-                            | (?P<ret>%s)\s*\b(?P<fn>pt_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
+                            | (?P<ret>%s)\s*\b(?P<fn>pto?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
                             | extern\s+"C"\s*\{ | \} )""" % _TYPE, re.X)
 _FIELD = re.compile(r"(%s)\s*\b(\w+(?:\s*,\s*\w+)*)" % _TYPE)         # `int32_t C0, C1`, `const void* x0`; a parameter is the one-name case
 
@@ -60,12 +63,12 @@ def _declarators(text: str, sep: str):
     return out
 
 
-def _parse_header(text: str):
+def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macro: str = "PT_ABI_VERSION"):
     """(PT_ABI_VERSION, {struct tag: Structure class}, {entry point: (C return type, [C parameter types])}).  Raises on
-    anything it does not understand; no declaration is skipped."""
-    version = re.search(r"^#define\s+PT_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    anything it does not understand; no declaration is skipped.  (The messages say posetraj_hip.h for either header.)"""
+    version = re.search(r"^#define\s+%s\s+(\d+)\s*$" % version_macro, text, flags=re.M)
     if not version:
-        raise ValueError("posetraj_hip.h: no `#define PT_ABI_VERSION n`")
+        raise ValueError(f"posetraj_hip.h: no `#define {version_macro} n`")
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
     structs, protos, pos = {}, {}, 0
@@ -75,15 +78,15 @@ def _parse_header(text: str):
             raise ValueError(f"posetraj_hip.h: cannot read the declaration {text[pos:].strip().split(';')[0][:200]!r}")
         if m.group("tag"):
             tag = m.group("tag")
-            if tag not in STRUCT_CLASSES:
+            if tag not in struct_classes:
                 raise ValueError(f"posetraj_hip.h: struct {tag!r} has no class name in posetraj_amd.hip.STRUCT_CLASSES")
             fields = [(n, _ctype(t, structs)) for t, n in _declarators(m.group("body"), ";")]
-            structs[tag] = type(STRUCT_CLASSES[tag], (C.Structure,), {"_fields_": fields, "__doc__": f"``{tag}`` of include/posetraj_hip.h."})
+            structs[tag] = type(struct_classes[tag], (C.Structure,), {"_fields_": fields, "__doc__": f"``{tag}`` of include/posetraj_hip.h."})
         elif m.group("fn"):
             params = m.group("params").strip()
             protos[m.group("fn")] = (" ".join(m.group("ret").split()), [] if params == "void" else [t for t, _ in _declarators(params, ",")])
         pos = m.end()
-    named = re.findall(r"pt_[a-z0-9_]+\s*\(", text)
+    named = re.findall(r"pto?_[a-z0-9_]+\s*\(", text)
     if len(named) != len(protos):
         raise ValueError(f"posetraj_hip.h: {len(named)} names are followed by '(' but {len(protos)} prototypes were read")
     return int(version.group(1)), structs, protos
@@ -94,6 +97,11 @@ with open(HEADER) as _f:
 IgemmParams, FfnParams, LnLinParams, ConvF32Params, GemmParams = (_STRUCTS[tag] for tag in STRUCT_CLASSES)         # in STRUCT_CLASSES' order
 # name -> (restype, argtypes); every symbol include/posetraj_hip.h declares
 SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in PROTOTYPES.items()}
+with open(OPTIM_HEADER) as _f:
+    OPTIM_ABI_VERSION, _OPTIM_STRUCTS, OPTIM_PROTOTYPES = _parse_header(_f.read(), OPTIM_STRUCT_CLASSES, "PT_OPTIM_ABI_VERSION")
+Adam8Segment = _OPTIM_STRUCTS["pt_adam8_segment"]
+OPTIM_SIGNATURES = {name: (_ctype(ret, _OPTIM_STRUCTS, returned=True), [_ctype(t, _OPTIM_STRUCTS) for t in params])
+                    for name, (ret, params) in OPTIM_PROTOTYPES.items()}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -104,7 +112,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -181,7 +189,7 @@ def source_digest() -> str:
     to replay them for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER]):
+    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER]):
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
     return h.hexdigest()
@@ -195,13 +203,15 @@ def _load(errcheck=None):
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(posetraj_amd has no CPU or PyTorch fallback path)")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)            # AttributeError if the symbol is missing
-        fn.restype, fn.argtypes = res, args
-        if errcheck is not None and PROTOTYPES[name][0] == "int" and name != "pt_abi_version":
-            fn.errcheck = errcheck
-    if L.pt_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} != expected {ABI_VERSION}; rebuild")
+    for sigs, protos in ((SIGNATURES, PROTOTYPES), (OPTIM_SIGNATURES, OPTIM_PROTOTYPES)):
+        for name, (res, args) in sigs.items():
+            fn = getattr(L, name)            # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version"):
+                fn.errcheck = errcheck
+    if L.pt_abi_version() != ABI_VERSION or L.pto_abi_version() != OPTIM_ABI_VERSION:
+        raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} / optimizer extension {L.pto_abi_version()} != expected "
+                           f"{ABI_VERSION} / {OPTIM_ABI_VERSION}; rebuild")
     return L
 
 

@@ -9,9 +9,9 @@ update (``pt_adamw_f32``) with fp16-mixed-precision loss scaling and gradient ac
 package's own models; their outputs are the step's inputs.  The camera twin (``controlnet_sdv_cam``, ``scripts/train_svd_traj_VIPSeg_14_cam_concat.py``: the same step with
 ``camera_cond`` and without the spatial loss) trains through the same class.  ``--use_ema`` (off in the launch scripts) is
 ``ControlNetTrainer(use_ema=True)``: diffusers' ``EMAModel`` over the ControlNet's parameters (``training_utils.py``), stepped inside
-the optimizer's pass.  Not here: the 8-bit
-optimizer (bitsandbytes), gradient checkpointing (activations of one 14-frame clip fit the 288 GB many times over), the data
-loader.
+the optimizer's pass.  ``--use_8bit_adam`` (``:1041-1049``, bitsandbytes' ``AdamW8bit``; off in the launch scripts) is
+``ControlNetTrainer(use_8bit_adam=True)``: block-quantised moments, updated by ``pto_adamw8_f32``.  Not here: gradient checkpointing
+(activations of one 14-frame clip fit the 288 GB many times over), the data loader.
 """
 from __future__ import annotations
 
@@ -222,6 +222,15 @@ class ControlNetTrainer:
     toward the unchanged parameters.  ``ema_state_dict()``: the averaged weights, for a validation pipeline or the final export.
     Data parallel: every rank keeps its own, identical shadow.  ``None`` (the default): no buffer, no launch, nothing in a checkpoint.
 
+    ``use_8bit_adam`` (``--use_8bit_adam``): AdamW's two moments are kept as 8-bit codes into two 256-entry books with one fp32
+    absmax per block of 256 stored elements (parameters under 4096 elements keep fp32 moments) - 2.03 bytes per parameter instead of
+    8; the full-size ``exp_avg`` / ``exp_avg_sq`` buffers are not allocated (``params.adam8`` holds the state,
+    ``training_utils.Adam8bitState``).  ``optimizer_step`` runs ``pto_adamw8_f32`` - torch's AdamW statements on the dequantised moments,
+    the fp16 mirror, the gradient's zeroing and the fused EMA in one launch, as the fp32 pass does - under the same GradScaler rules,
+    schedule and pack stream.  The format restates bitsandbytes' published blockwise quantisation; parity with the package is not
+    pinned.  Data parallel needs nothing new: the update is a deterministic function of the averaged gradients, so every
+    rank computes the same state.  Checkpoints of the two optimizer kinds do not load into each other.
+
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
 
@@ -232,7 +241,8 @@ class ControlNetTrainer:
                  bucket_mb: int = 256, wgrad_stream: bool = True, spatial_stream: bool = True, freeze_gc: bool = False,
                  lr_scheduler=None, use_graph: bool = False, device_scalars: Optional[bool] = None, encoder_stream: bool = True,
                  pack_stream: bool = True, use_ema: bool = False, ema_decay: float = 0.9999, ema_min_decay: float = 0.0,
-                 ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3):
+                 ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3,
+                 use_8bit_adam: bool = False):
         from . import autodiff as AD
         from . import grad_sync
         from . import train_graph as TG
@@ -241,7 +251,8 @@ class ControlNetTrainer:
             raise RuntimeError("ControlNetTrainer: the U-Net has no weights loaded")
         cfg = dict(controlnet_config)
         self.unet, self.device, self.config = unet, dev, cfg
-        self.params = AD.ParamStore(controlnet_state_dict, dev)
+        self.use_8bit_adam = bool(use_8bit_adam)
+        self.params = AD.ParamStore(controlnet_state_dict, dev, use_8bit_adam=self.use_8bit_adam)
         self.controlnet = TG.ControlNetGraph(self.params, cfg)
         self._frozen = AD.FrozenParams({k: v for k, v in unet.state_dict().items() if k.startswith(("up_blocks.", "conv_norm_out.", "conv_out."))}, dev)
         self.decoder = TG.UNetDecoderGraph(self._frozen, dict(unet.config))
@@ -512,15 +523,23 @@ class ControlNetTrainer:
                 self.last_lr = self.lr
             self.optimizer_steps += 1
             P = self.params
-            # AdamW + the fp16 mirror of the new parameters + the gradient's zeroing in ONE pass over the buffers
-            adamw = (P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel, self.last_lr, self.betas[0],
-                     self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, 1.0 / (self._accum_scale * self.world), P.flat16.data_ptr(), 1)
-            if ema is not None and self.ema_fused:        # ... and the EMA of the new parameters in the same pass
-                hip.checked().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream())
-            else:
-                hip.checked().pt_adamw_fused_f32(*adamw, ops._stream())
-                if ema is not None:
+            inv_scale = 1.0 / (self._accum_scale * self.world)
+            if P.adam8 is not None:                       # the same pass over block-quantised moments (and the EMA, when it is fused)
+                fused = ema is not None and self.ema_fused
+                P.adam8.step(self.last_lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, inv_scale,
+                             ema.shadow if fused else None, omd if fused else 0.0)
+                if ema is not None and not fused:
                     ema.update(omd)
+            else:
+                # AdamW + the fp16 mirror of the new parameters + the gradient's zeroing in ONE pass over the buffers
+                adamw = (P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel, self.last_lr, self.betas[0],
+                         self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, inv_scale, P.flat16.data_ptr(), 1)
+                if ema is not None and self.ema_fused:    # ... and the EMA of the new parameters in the same pass
+                    hip.checked().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream())
+                else:
+                    hip.checked().pt_adamw_fused_f32(*adamw, ops._stream())
+                    if ema is not None:
+                        ema.update(omd)
             P.version += 1
             P._mirror_version = P.version                 # (half_view() need not cast the buffer again)
             if self.pack_stream and self._packs_built and not self.use_graph:

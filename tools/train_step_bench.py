@@ -5,7 +5,9 @@ of the three families (pt_igemm_f16: forward and data gradients; pt_gemm_f16: we
 the memory high-water mark.
 
     python tools/train_step_bench.py [--steps 5] [--height 320 --width 576] [--frames 14] [--tiny] [--gemm-table] [--igemm-table]
-        [--temporal-bwd fused|recompute]
+        [--temporal-bwd fused|recompute] [--optimizer adamw|adamw8bit]
+    python tools/train_step_bench.py --optimizer-launch 3          # the optimizer's launch alone at the full parameter count: pt_adamw_fused_f32
+        against pto_adamw8_f32 (and their EMA forms), that many interleaved rounds
     python tools/train_step_bench.py --json --steps 7 --warmup 3      # what bench.py --train-step runs as a child process:
         wall-clock median without hipEvent brackets, the host's enqueue time, full garbage collections inside the timed steps
 """
@@ -39,6 +41,10 @@ def main():
     ap.add_argument("--temporal-bwd", choices=("fused", "recompute"), default="fused",
                     help="temporal attention backward of clips of 17 - 32 frames: pt_attn_temporal_bwd_f16 (autodiff.TEMPORAL_FLASH_FRAMES = 32) or the "
                          "recomputing path through pt_gemm_f16 (16)")
+    ap.add_argument("--optimizer", choices=("adamw", "adamw8bit"), default="adamw",
+                    help="adamw8bit: ControlNetTrainer(use_8bit_adam=True), block-quantised moments updated by pto_adamw8_f32")
+    ap.add_argument("--optimizer-launch", type=int, default=0, metavar="ROUNDS",
+                    help="time the optimizer launches alone over the ControlNet's parameter inventory (no network is built) and exit")
     ap.add_argument("--json", action="store_true", help="bench.py's train_step leg: time the steps without hipEvent brackets (median), count the matrix "
                                                       "flops in one extra bracketed step, print ONE JSON object")
     a = ap.parse_args()
@@ -47,6 +53,8 @@ def main():
     from posetraj_amd.training import ControlNetTrainer
     autodiff.TEMPORAL_FLASH_FRAMES = 32 if a.temporal_bwd == "fused" else 16
     dev = torch.device("cuda:0")
+    if a.optimizer_launch:
+        return optimizer_launch(a.optimizer_launch, a.tiny, dev)
     cfg = dict(num_attention_heads=(5, 10, 20, 20), num_frames=a.frames)
     ce = (16, 32, 96, 256)
     if a.tiny:
@@ -65,10 +73,11 @@ def main():
     del cn
     tr = ControlNetTrainer(ccfg, sd, unet, learning_rate=1e-5, conditioning_dropout_prob=0.1, freeze_gc=True, use_graph=a.graph,
                            wgrad_stream=not a.no_wgrad_stream, encoder_stream=not a.no_encoder_stream, spatial_stream=not a.no_spatial_stream, pack_stream=not a.no_pack_stream,
-                           use_ema=a.ema != "off")
+                           use_ema=a.ema != "off", use_8bit_adam=a.optimizer == "adamw8bit")
     tr.ema_fused = a.ema != "separate"
-    print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + 2 Adam moments"
-          f"{' + EMA shadow, ' + a.ema if a.ema != 'off' else ''})")
+    moments = "2 Adam moments" if tr.params.adam8 is None else f"8-bit Adam state, {tr.params.adam8.plan['state_bytes'] / 2 ** 20:.0f} MiB"
+    print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + {moments}"
+          f"{' + EMA shadow, ' + a.ema if a.ema != 'off' else ''})", file=sys.stderr if a.json else sys.stdout)
     h, w = a.height // 8, a.width // 8
     D = unet.config.cross_attention_dim
     lat = torch.randn(1, a.frames, 4, h, w, generator=g) * 0.18215 * 5
@@ -121,7 +130,7 @@ def main():
                           "matrix_TFLOP_per_step": round(flops / 1e12, 2), "peak_device_GiB": round(peak, 1),
                           "trainable_params_M": round(tr.params.numel / 1e6, 1), "loss_finite": bool(out["loss"] == out["loss"]),
                           "optimizer_stepped": bool(out["stepped"]), "hipgraph": bool(a.graph), "step_graphs": n_graphs,
-                          "graph_replays_in_timed_steps": int(sum(replayed)), **({"ema": a.ema} if a.ema != "off" else {}),
+                          "graph_replays_in_timed_steps": int(sum(replayed)), **({"ema": a.ema} if a.ema != "off" else {}), **({"optimizer": a.optimizer} if a.optimizer != "adamw" else {}),
                           "host_gc_in_timed_steps": [g for g in gc_log if g[1] >= 1.0], "streams": 1 + int(tr.wgrad_stream) + int(tr.spatial_stream and not a.no_spatial) + int(tr.encoder_stream)}))
         return
     L.pt_prof_enable(1)
@@ -185,6 +194,76 @@ def main():
         print(f"  {name:22s} {n:8.0f} launches  {ms:9.2f} ms  {fl / 1e12:8.2f} TFLOP  {fl / max(ms, 1e-9) / 1e9:8.1f} TFLOP/s")
     print(f"  matrix flops per step {tot_fl / 1e12:.1f} TFLOP -> {tot_fl / dt / 1e12:.0f} TFLOP/s over the whole step; "
           f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
+
+
+def optimizer_launch(rounds: int, tiny: bool, dev) -> None:
+    """The optimizer's launch alone over a store with the ControlNet's parameter inventory (random values, no network): the fp32 pass
+    and the 8-bit pass, without and with the fused EMA, `rounds` interleaved rounds of 5 launches behind 2 warm-up launches each;
+    hipEvent time per launch, median of each round."""
+    from posetraj_amd import ControlNetSDVModel, hip, ops
+    from posetraj_amd.autodiff import ParamStore
+    kw = dict(block_out_channels=(64, 64, 128, 128), num_attention_heads=(1, 1, 2, 2), cross_attention_dim=16, addition_time_embed_dim=8,
+              projection_class_embeddings_input_dim=24, layers_per_block=1, conditioning_embedding_out_channels=(8, 8, 16, 32)) if tiny else \
+        dict(num_attention_heads=(5, 10, 20, 20))
+    spec = ControlNetSDVModel(**kw).param_spec()
+
+    sd = {k: torch.empty(tuple(s), dtype=torch.float16, device="meta") for k, s in spec.items()}
+    stores = {}
+    for name, eight in (("adamw", False), ("adamw8bit", True)):
+        P = ParamStore.__new__(ParamStore)
+        P.names, P.offsets, n = list(sd), {}, 0
+        for k in P.names:
+            P.offsets[k] = n
+            n += (sd[k].numel() + 7) // 8 * 8
+        P.numel, P.shapes = n, {k: tuple(sd[k].shape) for k in P.names}
+        P.flat = torch.randn(n, device=dev) * 0.02
+        P.grad = torch.empty(n, device=dev)
+        P.flat16 = torch.empty(n, dtype=torch.float16, device=dev)
+        if eight:
+            from posetraj_amd.training_utils import Adam8bitState
+            P.adam8 = Adam8bitState(P)
+        else:
+            P.exp_avg, P.exp_avg_sq = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        stores[name] = P
+    shadow = stores["adamw"].flat.clone()
+    n = stores["adamw"].numel
+    A = stores["adamw8bit"].adam8
+    print(f"{n / 1e6:.1f} M parameters in {len(sd)} tensors; 8-bit state {A.plan['state_bytes'] / 2 ** 20:.0f} MiB against {8 * n / 2 ** 20:.0f} MiB "
+          f"({A.plan['n_blocks']} blocks, {A.plan['n_f32']} elements with fp32 moments)")
+    L, st = hip.checked(), ops._stream()
+    hyper = (1e-5, 0.9, 0.999, 1e-8, 1e-2)
+    step = [0]
+
+    def launch(which, ema):
+        P = stores[which]
+        P.grad.normal_()                                       # (outside the events) a fresh gradient: the pass zeroes it
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step[0] += 1
+        e0.record()
+        if which == "adamw8bit":
+            P.adam8.step(*hyper, step[0], 1.0, shadow if ema else None, 0.0001)
+        elif ema:
+            L.pt_adamw_ema_f32(P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), n, *hyper, step[0], 1.0,
+                               P.flat16.data_ptr(), 1, shadow.data_ptr(), 0.0001, st)
+        else:
+            L.pt_adamw_fused_f32(P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), n, *hyper, step[0], 1.0,
+                                 P.flat16.data_ptr(), 1, st)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+    legs = [("adamw", False), ("adamw8bit", False), ("adamw", True), ("adamw8bit", True)]
+    res = {leg: [] for leg in legs}
+    for r in range(rounds):
+        for leg in legs:
+            for _ in range(2):
+                launch(*leg)
+            tt = sorted(launch(*leg) for _ in range(5))
+            res[leg].append(tt[2])
+    for leg in legs:
+        print(f"  {leg[0]:10s} {'+ EMA' if leg[1] else '     '}  ms per launch, median of 5, per round: " + "  ".join(f"{v:.3f}" for v in res[leg]))
+    for ema in (False, True):
+        a32, a8 = sorted(res[("adamw", ema)])[rounds // 2], sorted(res[("adamw8bit", ema)])[rounds // 2]
+        print(f"  8-bit / fp32 {'with' if ema else 'without'} EMA: {a8 / a32:.3f}")
 
 
 if __name__ == "__main__":
