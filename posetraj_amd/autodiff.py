@@ -46,6 +46,37 @@ class Tape:
         self._ops.clear()
 
 
+def checkpoint(tape: Tape, fn: Callable[[Tape], Var]) -> Var:
+    """Gradient checkpointing of one segment of the forward (``--gradient_checkpointing``; ``torch.utils.checkpoint`` in the reference's
+    networks): ``fn(t)`` builds the segment on the tape it is given, from ``Var``s it closes over, and returns the segment's output.
+
+    Forward: ``fn`` runs on a scratch tape whose closures are dropped at once - every intermediate of the segment dies with them, only
+    the output tensor survives.  Backward (ONE closure on ``tape``): ``fn`` runs again on a fresh tape - the forward kernels are
+    bit-reproducible, so the recomputed activations are the dropped ones - the output's gradient is handed to the new output and the
+    fresh tape is reversed, each closure released as soon as it has run, so the segment's memory falls during its own reverse pass.
+    Gradients reach the segment's inputs through ``_acc`` on the very ``Var``s ``fn`` closes over (those used outside the
+    segment as well: nothing is re-wrapped).  A primitive's side effects - weight gradients, ``grad_ready`` - live in its backward
+    closure and so still happen once per micro-batch; a segment whose output receives no gradient is not recomputed."""
+    scratch = Tape()
+    out = fn(scratch)
+    del scratch                                       # its closures held the segment's intermediates
+
+    def bwd():
+        dy, out.g = out.g, None
+        if dy is None:
+            return
+        local = Tape()
+        again = fn(local)
+        again.g = dy
+        del again, dy
+        ops_ = local._ops
+        while ops_:
+            ops_.pop()()
+
+    tape.record(bwd)
+    return out
+
+
 WGRAD_STREAM: Optional[torch.cuda.Stream] = None      # set by the trainer: weight gradients run beside the data gradients
 
 

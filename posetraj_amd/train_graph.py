@@ -112,6 +112,13 @@ class Transformer:
         return AD.dense(tape, h, self.proj_out, res=x)
 
 
+def _segment(tape: Tape, checkpoint: bool, fn) -> Var:
+    """One ``ResBlock.run`` / ``Transformer.run`` call ``fn(t)``: on ``tape`` itself, or as a checkpointed segment of it
+    (``AD.checkpoint``: activations dropped after the forward and recomputed in the reverse pass).  Everything between the segments -
+    convolutions in and out, samplers, zero-convs, the residual adds - stays on the outer tape either way."""
+    return AD.checkpoint(tape, fn) if checkpoint else fn(tape)
+
+
 def _count(P, fmt):
     i = 0
     while P.has(fmt.format(i)):
@@ -174,9 +181,10 @@ class ControlNetGraph:
         self.zero_mid = zc("controlnet_mid_block")
 
     def run(self, tape: Tape, sample_cl: torch.Tensor, geom, timestep, ehs: torch.Tensor, added_time_ids, cond: torch.Tensor,
-            conditioning_scale: float = 1.0, camera_cond: Optional[torch.Tensor] = None):
+            conditioning_scale: float = 1.0, camera_cond: Optional[torch.Tensor] = None, checkpoint: bool = False):
         """``sample_cl``: the network input channels-last ``[F h w, 8]``; ``cond``: ``[F, 3, H, W]`` trajectory maps; ``camera_cond``:
-        ``[F, 12]`` (R|T per frame) for the camera twin."""
+        ``[F, 12]`` (R|T per frame) for the camera twin.  ``checkpoint``: every residual block and every transformer is a
+        checkpointed segment (``controlnet.enable_gradient_checkpointing()``)."""
         N, h, w = geom
         dev = sample_cl.device
         ctx = TrainCtx(N, self.time.run(tape, timestep, added_time_ids, dev), Var(ehs, need=False))
@@ -201,15 +209,16 @@ class ControlNetGraph:
         g = geom
         for blk in self.down:
             for j, r in enumerate(blk.resnets):
-                x = r.run(tape, ctx, x, g)
+                x = _segment(tape, checkpoint, lambda t, r=r, x=x, g=g: r.run(t, ctx, x, g))
                 if blk.attns:
-                    x = blk.attns[j].run(tape, ctx, x, g)
+                    x = _segment(tape, checkpoint, lambda t, a=blk.attns[j], x=x, g=g: a.run(t, ctx, x, g))
                 taps.append(x)
             if blk.down is not None:
                 x = AD.dense(tape, x, blk.down, geom=g)
                 g = (g[0], (g[1] + 1) // 2, (g[2] + 1) // 2)
                 taps.append(x)
-        x = self.mid[2].run(tape, ctx, self.mid[1].run(tape, ctx, self.mid[0].run(tape, ctx, x, g), g), g)
+        for m in self.mid:
+            x = _segment(tape, checkpoint, lambda t, m=m, x=x, g=g: m.run(t, ctx, x, g))
         if conditioning_scale != 1.0:
             raise NotImplementedError("training uses conditioning_scale = 1.0 (controlnet_sdv.py:527)")
         outs = [AD.dense(tape, t, z) for t, z in zip(taps, self.zero)]
@@ -237,8 +246,10 @@ class UNetDecoderGraph:
         self.norm_out = Affine(P, "conv_norm_out")
         self.conv_out = Dense(P, "conv_out.weight", "conv_out.bias", kind="conv", padding=1)
 
-    def run(self, tape: Tape, state: dict, mult: List[int], residuals: List[Var], mid_residual: Var, emb_silu: torch.Tensor, ehs: torch.Tensor) -> Var:
-        """``state``: what ``UNetSpatioTemporalConditionControlNetModel._encode`` returned (inference kernels)."""
+    def run(self, tape: Tape, state: dict, mult: List[int], residuals: List[Var], mid_residual: Var, emb_silu: torch.Tensor, ehs: torch.Tensor,
+            checkpoint: bool = False) -> Var:
+        """``state``: what ``UNetSpatioTemporalConditionControlNetModel._encode`` returned (inference kernels).  ``checkpoint``: every
+        residual block (two-source: it closes over its skip) and every transformer is a checkpointed segment."""
         Bc, F = state["dims"]
         ctx = TrainCtx(F, Var(emb_silu, need=False), Var(ehs, need=False))
         skips = []
@@ -253,9 +264,9 @@ class UNetDecoderGraph:
                 skip, sg = skips.pop()
                 if sg != g:
                     raise RuntimeError(f"Sizes of tensors must match except in dimension 1: {g} vs {sg}")
-                x = r.run(tape, ctx, x, g, x1=skip)
+                x = _segment(tape, checkpoint, lambda t, r=r, x=x, g=g, skip=skip: r.run(t, ctx, x, g, x1=skip))
                 if blk.attns:
-                    x = blk.attns[j].run(tape, ctx, x, g)
+                    x = _segment(tape, checkpoint, lambda t, a=blk.attns[j], x=x, g=g: a.run(t, ctx, x, g))
             if blk.up is not None:
                 x = AD.dense(tape, x, blk.up, geom=g, upsample2x=True)
                 g = (g[0], 2 * g[1], 2 * g[2])

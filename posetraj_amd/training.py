@@ -10,8 +10,10 @@ package's own models; their outputs are the step's inputs.  The camera twin (``c
 ``camera_cond`` and without the spatial loss) trains through the same class.  ``--use_ema`` (off in the launch scripts) is
 ``ControlNetTrainer(use_ema=True)``: diffusers' ``EMAModel`` over the ControlNet's parameters (``training_utils.py``), stepped inside
 the optimizer's pass.  ``--use_8bit_adam`` (``:1041-1049``, bitsandbytes' ``AdamW8bit``; off in the launch scripts) is
-``ControlNetTrainer(use_8bit_adam=True)``: block-quantised moments, updated by ``pto_adamw8_f32``.  Not here: gradient checkpointing
-(activations of one 14-frame clip fit the 288 GB many times over), the data loader.
+``ControlNetTrainer(use_8bit_adam=True)``: block-quantised moments, updated by ``pto_adamw8_f32``.  ``--gradient_checkpointing``
+(``:1025-1026``, ON in every launch script) is ``ControlNetTrainer(gradient_checkpointing=True)``: every residual block and transformer
+of the ControlNet is a checkpointed segment of the tape (``autodiff.checkpoint``) - its activations are dropped after the forward and
+recomputed, by the same kernels, in the reverse pass.  Not here: the data loader.
 """
 from __future__ import annotations
 
@@ -231,6 +233,17 @@ class ControlNetTrainer:
     pinned.  Data parallel needs nothing new: the update is a deterministic function of the averaged gradients, so every
     rank computes the same state.  Checkpoints of the two optimizer kinds do not load into each other.
 
+    ``gradient_checkpointing`` (``--gradient_checkpointing`` / ``controlnet.enable_gradient_checkpointing()``): ``False`` (the default)
+    keeps every activation, launch for launch the step as it was; ``True`` is the reference's flag - each ``ResBlock`` / ``Transformer``
+    of the ControlNet runs as ``autodiff.checkpoint``: only its output survives the forward, and the reverse pass re-runs it (the forward
+    kernels are bit-reproducible, so the recomputed activations are the dropped ones) before reversing it; ``"all"`` does the same to the
+    frozen decoder's blocks in the temporal pass and in the one-frame spatial pass, whose recomputation stays on the spatial stream -
+    which the reference, differentiating through an un-checkpointed U-Net, cannot.  Losses are the same launches in every mode;
+    gradients differ by the order of the backward's fp32 atomics only.  The price is one more ControlNet forward per step
+    (``"all"``: and one more decoder forward); what it buys is in DESIGN 4.13.  Accumulation, the GradScaler skip, ``use_ema``,
+    ``use_8bit_adam``, data parallel and the side streams are untouched - the segments' weight gradients and ``grad_ready`` calls
+    happen in the same order, once per micro-batch - and a checkpoint file knows nothing of the mode.  Not with ``use_graph``.
+
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
 
@@ -242,13 +255,21 @@ class ControlNetTrainer:
                  lr_scheduler=None, use_graph: bool = False, device_scalars: Optional[bool] = None, encoder_stream: bool = True,
                  pack_stream: bool = True, use_ema: bool = False, ema_decay: float = 0.9999, ema_min_decay: float = 0.0,
                  ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3,
-                 use_8bit_adam: bool = False):
+                 use_8bit_adam: bool = False, gradient_checkpointing=False):
         from . import autodiff as AD
         from . import grad_sync
         from . import train_graph as TG
         dev = unet.device
         if dev is None:
             raise RuntimeError("ControlNetTrainer: the U-Net has no weights loaded")
+        if not any(gradient_checkpointing is v for v in (False, True)) and gradient_checkpointing != "all":
+            raise ValueError(f"ControlNetTrainer: gradient_checkpointing must be False, True or \"all\"; got {gradient_checkpointing!r}")
+        if use_graph and gradient_checkpointing:
+            raise ValueError("ControlNetTrainer(use_graph=True) does not take gradient_checkpointing: the captured step exists to cut host "
+                             "time, which the recomputation's launches add to, and it holds its buffers in one pool for the graph's "
+                             "lifetime anyway, so dropping activations frees nothing")
+        self.gradient_checkpointing = gradient_checkpointing
+        self._ckpt_cn, self._ckpt_dec = bool(gradient_checkpointing), gradient_checkpointing == "all"
         cfg = dict(controlnet_config)
         self.unet, self.device, self.config = unet, dev, cfg
         self.use_8bit_adam = bool(use_8bit_adam)
@@ -425,7 +446,8 @@ class ControlNetTrainer:
         if self._packs_pending:                               # the packs re-written behind the last optimizer step (their own stream)
             main.wait_stream(self._pk_stream)
             self._packs_pending = False
-        outs, mid = self.controlnet.run(tape_cn, I["x"].view(F * h * w, 8), (F, h, w), timesteps, ehs16, ids, I["traj"][0], camera_cond=cam)
+        outs, mid = self.controlnet.run(tape_cn, I["x"].view(F * h * w, 8), (F, h, w), timesteps, ehs16, ids, I["traj"][0], camera_cond=cam,
+                                        checkpoint=self._ckpt_cn)
         with torch.no_grad():
             emb_silu = unet.time.run(timesteps, ids, 1)
 
@@ -456,7 +478,7 @@ class ControlNetTrainer:
                 mult_s = unet._multiplicity(state_s, len(outs))
                 res_s = [AD.rows(tape_sp, o, ran_idx * (o.v.shape[0] // F), (ran_idx + 1) * (o.v.shape[0] // F), defer=deferred) for o in outs]
                 mid_s = AD.rows(tape_sp, mid, ran_idx * (mid.v.shape[0] // F), (ran_idx + 1) * (mid.v.shape[0] // F), defer=deferred)
-                pred_s = self.decoder.run(tape_sp, state_s, mult_s, res_s, mid_s, emb_silu, ehs16)
+                pred_s = self.decoder.run(tape_sp, state_s, mult_s, res_s, mid_s, emb_silu, ehs16, checkpoint=self._ckpt_dec)
                 ls = loss_of(pred_s, noisy[:, ran_idx:ran_idx + 1].contiguous(), lat[:, ran_idx:ran_idx + 1].contiguous(), 1, 0.5)
         if state is None:
             with torch.no_grad():
@@ -469,7 +491,7 @@ class ControlNetTrainer:
                     if getattr(tns, "lo", None) is not None:
                         tns.lo.record_stream(main)
         mult = unet._multiplicity(state, len(outs))
-        pred = self.decoder.run(tape, state, mult, outs, mid, emb_silu, ehs16)
+        pred = self.decoder.run(tape, state, mult, outs, mid, emb_silu, ehs16, checkpoint=self._ckpt_dec)
         lt = loss_of(pred, noisy, lat, F, 1.0)
         sync = self._micro + 1 >= self.accumulation          # inside an accumulation cycle only the last micro-batch synchronises
         if sync:
