@@ -10,6 +10,11 @@ activation, reduction and the optimizer update is a kernel of this library, and 
 
 Precision follows ``--mixed_precision="fp16"`` of the reference's launch scripts (``start_ft.sh``): fp32 master parameters and
 gradients, fp16 activations and activation gradients, the loss scaled before the reverse pass (``GradScaler`` semantics).
+
+The gradient hand-over is ONE protocol, ``Tape.op(out, bwd)``: in the reverse pass the output's gradient is taken off ``out`` (so it
+lives no longer than this closure), ``bwd(dy)`` runs only if one arrived, and gradients go on to the inputs through ``_acc`` on the
+``Var``s the closure holds.  Every primitive records itself that way; ``Tape.record(fn)`` takes a bare closure and is for wrappers
+that manage the gradient's lifetime themselves (``checkpoint``).
 """
 from __future__ import annotations
 
@@ -40,7 +45,22 @@ class Tape:
     def record(self, fn: Callable[[], None]) -> None:
         self._ops.append(fn)
 
-    def backward(self) -> None:
+    def op(self, out: Var, bwd: Callable[[torch.Tensor], None]) -> None:
+        """A primitive's backward: take ``out``'s gradient off it; ``bwd(dy)`` if there is one."""
+        def run():
+            dy, out.g = out.g, None
+            if dy is not None:
+                bwd(dy)
+
+        self._ops.append(run)
+
+    def backward(self, release: bool = False) -> None:
+        """Run the closures in reverse.  They are dropped together at the end, or with ``release`` each one as soon as it has run
+        (what it alone held dies before the next one starts)."""
+        if release:
+            while self._ops:
+                self._ops.pop()()
+            return
         for fn in reversed(self._ops):
             fn()
         self._ops.clear()
@@ -56,7 +76,11 @@ def checkpoint(tape: Tape, fn: Callable[[Tape], Var]) -> Var:
     fresh tape is reversed, each closure released as soon as it has run, so the segment's memory falls during its own reverse pass.
     Gradients reach the segment's inputs through ``_acc`` on the very ``Var``s ``fn`` closes over (those used outside the
     segment as well: nothing is re-wrapped).  A primitive's side effects - weight gradients, ``grad_ready`` - live in its backward
-    closure and so still happen once per micro-batch; a segment whose output receives no gradient is not recomputed."""
+    closure and so still happen once per micro-batch; a segment whose output receives no gradient is not recomputed.
+
+    On ``Tape.record``, not ``Tape.op``: this closure gives up its last reference to the output's gradient BEFORE the segment is
+    reversed, so that tensor can die in the middle of the segment's reverse pass; under ``op`` the caller's frame would hold it until
+    the whole segment is through."""
     scratch = Tape()
     out = fn(scratch)
     del scratch                                       # its closures held the segment's intermediates
@@ -69,9 +93,7 @@ def checkpoint(tape: Tape, fn: Callable[[Tape], Var]) -> Var:
         again = fn(local)
         again.g = dy
         del again, dy
-        ops_ = local._ops
-        while ops_:
-            ops_.pop()()
+        local.backward(release=True)
 
     tape.record(bwd)
     return out
@@ -211,13 +233,7 @@ class ParamStore:
         what ``Dense.packs()`` would do lazily, layer by layer, in the middle of the next forward (~400 launches of ~9 us in its
         serial chain: 3.5 ms of a 97 ms step).  The trainer calls this right behind AdamW on a stream of its own, so the launches run
         while the host stages the next step's inputs and beside the frozen encoder that opens it.  Returns the number of layers."""
-        n = 0
-        for L in self.layers:
-            if L._packs is not None and L._packs[0] != self.version:
-                L._refresh(L._packs[1], L._packs[2])
-                L._packs = (self.version, L._packs[1], L._packs[2])
-                n += 1
-        return n
+        return sum(L.refresh() for L in self.layers)
 
     def refresh_alphas(self) -> None:
         """``alphas[i] = sigmoid(scalar i)`` from the fp32 master buffer; enqueued at the start of every step in device-scalar mode."""
@@ -242,13 +258,14 @@ class ParamStore:
             self._scalars = (self.version, dict(zip(self._scalar_names, vals)))
         return self._scalars[1][k]
 
+    def count(self, k) -> int:
+        """The parameter's number of elements."""
+        return math.prod(self.shapes[k])
+
     def raw(self, buf, k):
         """The parameter's flat slice of ``buf`` (tap-major for convolution weights)."""
         o = self.offsets[k]
-        n = 1
-        for s in self.shapes[k]:
-            n *= s
-        return buf[o:o + n]
+        return buf[o:o + self.count(k)]
 
     def layout(self, k):
         """``(T, Co, Ci)`` of a weight (T = taps; 1 for a linear layer), None for vectors / scalars."""
@@ -314,13 +331,7 @@ class ParamStore:
 
     def spans(self):
         """name -> (start, numel) inside the flat buffers (grad_sync.GradientBuckets)."""
-        out = {}
-        for k in self.names:
-            n = 1
-            for s in self.shapes[k]:
-                n *= s
-            out[k] = (self.offsets[k], n)
-        return out
+        return {k: (self.offsets[k], self.count(k)) for k in self.names}
 
     def grad_ready(self, *names):
         """The reverse pass has finished the gradients of ``names`` (every trainable layer is used once per step): the
@@ -378,13 +389,17 @@ class Dense:
         self.bname = bname if (bname is not None and P.has(bname)) else None
         self._packs = None
         if isinstance(P, ParamStore):
-            P.layers.append(self)                     # (ParamStore.refresh_packs re-writes every trainable layer's packs in one go)
+            P.layers.append(self)                     # (ParamStore.refresh_packs refreshes every trainable layer in one go)
 
     def weight(self):
         return self.P.stacked(self.stack) if self.stack else self.P.value(self.wname)
 
-    def _refresh(self, f, t):
-        """Rewrite both packs in place from the fp32 master (pt_pack_weight_f32): same buffers, same addresses."""
+    def refresh(self) -> bool:
+        """If the packs exist and the optimizer has moved the master since, rewrite both in place from the fp32 master
+        (pt_pack_weight_f32): same buffers, same addresses.  Returns whether it did."""
+        if self._packs is None or self._packs[0] == self.P.version or not isinstance(self.P, ParamStore):
+            return False
+        _, f, t = self._packs
         src, (T, Co, Ci) = self._raw(self.P.flat)
         if self.kind == "linear":
             Ci, T = Ci * T, 1                         # a 1 x 1 convolution's weight used as a matrix
@@ -397,6 +412,8 @@ class Dense:
         L = hip.checked()
         L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 0, _ptr(b), f.w.data_ptr(), f.Kpad, cpf, _ptr(f.bias), _stream())
         L.pt_pack_weight_f32(src.data_ptr(), Co, Ci, T, 1, None, t.w.data_ptr(), t.Kpad, cpt, None, _stream())
+        self._packs = (self.P.version, f, t)
+        return True
 
     def _raw(self, buf):
         """The weight's flat (tap-major) slice of ``buf`` and its (T, Co, Ci); stacked layers: the adjacent matrices as one."""
@@ -407,10 +424,11 @@ class Dense:
         return P.raw(buf, self.wname), P.layout(self.wname)
 
     def packs(self):
-        if self._packs is not None and self._packs[0] != self.P.version and isinstance(self.P, ParamStore):
-            self._refresh(self._packs[1], self._packs[2])
-            self._packs = (self.P.version, self._packs[1], self._packs[2])
-        if self._packs is None or self._packs[0] != self.P.version:
+        """The forward and the data-gradient pack: built through the torch packing path the first time, refreshed in place when a
+        ``ParamStore``'s optimizer has moved the master (a frozen store never moves)."""
+        if self._packs is not None:
+            self.refresh()
+        else:
             w = self.weight().detach()
             b = None if self.bname is None else self.P.value(self.bname)
             dev = w.device
@@ -505,6 +523,14 @@ class Mix:
     def __init__(self, P, name):
         self.P, self.name, self._c = P, name, None
 
+    def ptr(self) -> Optional[int]:
+        """Where the weight lives.  A trainable store with ``device_scalars``: its address in device memory (``ParamStore.alphas``) -
+        it changes with every optimizer step, and a launch that reads it from memory can be replayed inside a captured hipGraph
+        (``ControlNetTrainer(use_graph=True)``).  Otherwise None: ``alpha()`` is passed as a host float (the frozen U-Net's weights
+        are constants of a capture)."""
+        P = self.P
+        return P.alpha_ptr(self.name) if P.trainable and getattr(P, "device_scalars", False) else None
+
     def alpha(self) -> float:
         if self._c is None or self._c[0] != self.P.version:
             self._c = (self.P.version, 1.0 / (1.0 + math.exp(-self.P.scalar(self.name))))
@@ -523,10 +549,7 @@ def dense(tape: Tape, x: Var, L: Dense, *, geom=None, res: Optional[Var] = None,
         y = ops.igemm(x.v, fwd, geom=geom, x1=None if x1 is None else x1.v, upsample2x=upsample2x, res=None if res is None else res.v)
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         _acc(res, dy)
         if x1 is None and L.P.trainable:
             _beside(lambda: L.accumulate(x.v, dy, geom), x.v, dy)
@@ -557,7 +580,7 @@ def dense(tape: Tape, x: Var, L: Dense, *, geom=None, res: Optional[Var] = None,
         if x1 is not None:
             _acc(x1, gx[1])
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -568,10 +591,7 @@ def groupnorm(tape: Tape, x: Var, A: Affine, *, rows_per_sample: int, n_samples:
                       x1=None if x1 is None else x1.v, groups=groups)
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         C0 = x.v.shape[-1]
         C1 = 0 if x1 is None else x1.v.shape[-1]
         rows = rows_per_sample * n_samples
@@ -587,7 +607,7 @@ def groupnorm(tape: Tape, x: Var, A: Affine, *, rows_per_sample: int, n_samples:
         if x1 is not None:
             _acc(x1, dx1)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -595,10 +615,7 @@ def layernorm(tape: Tape, x: Var, A: Affine, eps: float = 1e-5) -> Var:
     gm, bt = A.halves()
     out = Var(ops.layernorm(x.v, gm, bt, eps))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         M, Cc = x.v.shape
         dx = torch.empty_like(x.v)
         dg, db = A.grads()
@@ -608,22 +625,21 @@ def layernorm(tape: Tape, x: Var, A: Affine, eps: float = 1e-5) -> Var:
         A.P.grad_ready(A.w, A.b)
         _acc(x, dx)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
 def silu(tape: Tape, x: Var) -> Var:
     out = Var(ops.silu(x.v))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None or not x.need:
+    def bwd(dy):
+        if not x.need:
             return
         dx = torch.empty_like(x.v)
         hip.checked().pt_silu_bwd(x.v.data_ptr(), dy.data_ptr(), x.v.numel(), dx.data_ptr(), _stream())
         _acc(x, dx)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -635,29 +651,23 @@ def geglu(tape: Tape, h: Var) -> Var:
     hip.checked().pt_geglu_f16(h.v.data_ptr(), M, I, y.data_ptr(), _stream())
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         dh = torch.empty_like(h.v)
         hip.checked().pt_geglu_bwd(h.v.data_ptr(), dy.data_ptr(), M, I, dh.data_ptr(), _stream())
         _acc(h, dh)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
 def add(tape: Tape, a: Var, b: Var) -> Var:
     out = Var(ops.axpy(a.v, b.v, 1.0).view(a.v.shape))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         _acc(a, dy)
         _acc(b, dy)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -665,12 +675,7 @@ def add_scaled_const(tape: Tape, const: torch.Tensor, r: Var, m: float) -> Var:
     """``const + m * r`` where ``const`` carries no gradient (a U-Net skip receiving its ControlNet residual m times)."""
     out = Var(ops.axpy(const.reshape(r.v.shape), r.v, float(m)))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is not None:
-            _acc(r, dy if m == 1 else ops.scale(dy, float(m)))
-
-    tape.record(bwd)
+    tape.op(out, lambda dy: _acc(r, dy if m == 1 else ops.scale(dy, float(m))))
     return out
 
 
@@ -681,10 +686,7 @@ def add_rowvec(tape: Tape, x: Var, vec: Var, rows_per_vec: int) -> Var:
     hip.checked().pt_add_rowvec_f16(x.v.data_ptr(), vec.v.data_ptr(), rows, Cc, rows_per_vec, y.data_ptr(), _stream())
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
+    def bwd(dy):
         _acc(x, dy)
         if vec.need:
             nseg = rows // rows_per_vec
@@ -692,54 +694,41 @@ def add_rowvec(tape: Tape, x: Var, vec: Var, rows_per_vec: int) -> Var:
             colsum(dy, rows_per_vec, nseg, s)
             _acc(vec, s.to(torch.float16))
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
 def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
     """AlphaBlender (``merge_strategy="learned_with_images"`` with an all-zero indicator): ``alpha a + (1 - alpha) b``."""
+    L, ap = hip.checked(), M.ptr()
+    al = M.alpha() if ap is None else None
     y = torch.empty_like(a.v)
-    if M.P.trainable and getattr(M.P, "device_scalars", False):
-        # the weight changes with every optimizer step: read from device memory (ParamStore.alphas), so that the launch can be replayed
-        # inside a captured hipGraph (ControlNetTrainer(use_graph=True)); the frozen U-Net's weights below are constants of the capture
-        ap = M.P.alpha_ptr(M.name)
-        L = hip.checked()
+    if ap is None:
+        L.pt_lerp_f16(a.v.data_ptr(), b.v.data_ptr(), al, a.v.numel(), y.data_ptr(), _stream())
+    else:
         L.pt_lerp_f16_dev(a.v.data_ptr(), b.v.data_ptr(), ap, a.v.numel(), y.data_ptr(), _stream())
-        out = Var(y)
-
-        def scaled(dy, one_minus):
-            d = dy.contiguous()
-            z = torch.empty_like(d)
-            L.pt_scale_f16_dev(d.data_ptr(), ap, one_minus, d.numel(), z.data_ptr(), _stream())
-            return z
-
-        def bwd_dev():
-            dy, out.g = out.g, None
-            if dy is None:
-                return
-            L.pt_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, M.P.gradient(M.name).data_ptr(), _stream())
-            M.P.grad_ready(M.name)
-            _acc(a, scaled(dy, 0))
-            _acc(b, scaled(dy, 1))
-
-        tape.record(bwd_dev)
-        return out
-    al = M.alpha()
-    hip.checked().pt_lerp_f16(a.v.data_ptr(), b.v.data_ptr(), al, a.v.numel(), y.data_ptr(), _stream())
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
-        if M.P.trainable:                                       # d alpha / d mix = alpha (1 - alpha)
-            hip.checked().pt_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al),
-                                      M.P.gradient(M.name).data_ptr(), _stream())
-            M.P.grad_ready(M.name)
-        _acc(a, ops.scale(dy, al))
-        _acc(b, ops.scale(dy, 1.0 - al))
+    def scaled(dy, one_minus):
+        if ap is None:
+            return ops.scale(dy, 1.0 - al if one_minus else al)
+        d = dy.contiguous()
+        z = torch.empty_like(d)
+        L.pt_scale_f16_dev(d.data_ptr(), ap, one_minus, d.numel(), z.data_ptr(), _stream())
+        return z
 
-    tape.record(bwd)
+    def bwd(dy):
+        if M.P.trainable:                                       # d alpha / d mix = alpha (1 - alpha): on the host, or in the kernel
+            gm = M.P.gradient(M.name).data_ptr()
+            if ap is None:
+                L.pt_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al), gm, _stream())
+            else:
+                L.pt_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, gm, _stream())
+            M.P.grad_ready(M.name)
+        _acc(a, scaled(dy, 0))
+        _acc(b, scaled(dy, 1))
+
+    tape.op(out, bwd)
     return out
 
 
@@ -749,17 +738,13 @@ def concat_camera(tape: Tape, x: Var, geom, cam: torch.Tensor, cpad: int) -> Var
     N, H, W = geom
     out = Var(ops.concat_camera(x.v.view(N, H, W, -1), cam, cpad).view(N * H * W, cpad))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is not None:
-            _acc(x, dy)
-
-    tape.record(bwd)
+    tape.op(out, lambda dy: _acc(x, dy))
     return out
 
 
 def add_rows(x: Var, r0: int, r1: int, dy: torch.Tensor) -> None:
-    """``x.g[r0:r1] += dy`` on the current stream (the join of a deferred ``rows`` gradient)."""
+    """``x.g[r0:r1] += dy`` on the current stream, into a clone or a zero fill - never in place, ``x.g`` may be another variable's
+    gradient too: the backward of ``rows``, at once or as the join of a deferred one."""
     if not x.need:
         return
     x.g = torch.zeros_like(x.v) if x.g is None else x.g.clone()
@@ -773,21 +758,13 @@ def rows(tape: Tape, x: Var, r0: int, r1: int, defer: Optional[list] = None) -> 
     joins with ``add_rows`` once both streams are in."""
     out = Var(x.v[r0:r1])
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None or not x.need:
-            return
-        if defer is not None:
+    def bwd(dy):
+        if defer is None:
+            add_rows(x, r0, r1, dy)
+        elif x.need:
             defer.append((x, r0, r1, dy))
-            return
-        if x.g is None:
-            x.g = torch.zeros_like(x.v)
-        else:
-            x.g = x.g.clone()
-        sl = x.g[r0:r1]
-        hip.checked().pt_axpy_f16(sl.data_ptr(), dy.data_ptr(), 1.0, sl.data_ptr(), sl.numel(), _stream())
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -826,6 +803,14 @@ def _attention_backward(qkv: torch.Tensor, dout: torch.Tensor, Cc: int, heads: i
     return dqkv
 
 
+def _one_key_backward(qkv: torch.Tensor, dout: torch.Tensor, Cc: int) -> torch.Tensor:
+    """Attention over ONE key: softmax over one logit is 1, out = V -> dV = dO and dQ = dK = 0 EXACTLY (the kernels' dP - Dq cancels
+    to rounding only: ~1e-7 of dP)."""
+    dqkv = torch.zeros_like(qkv)
+    dqkv[:, 2 * Cc:].copy_(dout)
+    return dqkv
+
+
 ATTN_SCORE_BYTES = 2 << 30          # score-matrix memory (fp32) the recomputing attention backward holds at a time
 FLASH_BACKWARD = True               # spatial attention: pt_attn_fwd_lse_f16 / pt_attn_bwd_f16 (False: recompute through pt_gemm_f16)
 TEMPORAL_FLASH_FRAMES = 32          # temporal attention: clips up to this many frames take pt_attn_temporal_bwd_f16 (16: longer ones recompute)
@@ -850,14 +835,9 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
         y = ops.attention(qkv.v[:, :Cc], qkv.v[:, Cc:2 * Cc], qkv.v[:, 2 * Cc:], N, S, S, heads, hd)
     out = Var(y)
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
-        if S == 1:                                   # one position (the mid block of an 8 x 8 latent): like one frame below, dV = dO and
-            dqkv = torch.zeros_like(qkv.v)           # dQ = dK = 0 EXACTLY (the kernels' dP - Dq cancels to rounding only: ~1e-7 of dP)
-            dqkv[:, 2 * Cc:].copy_(dy)
-            _acc(qkv, dqkv)
+    def bwd(dy):
+        if S == 1:                                   # one position (the mid block of an 8 x 8 latent)
+            _acc(qkv, _one_key_backward(qkv.v, dy, Cc))
             return
         if not flash:
             chunk = max(1, ATTN_SCORE_BYTES // (heads * S * S * 4))
@@ -870,7 +850,7 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
                                       dot.data_ptr(), d0, d0 + 2 * Cc, d0 + 4 * Cc, dqkv.stride(0), N, S, heads, hd, hd ** -0.5, _stream())
         _acc(qkv, dqkv)
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out
 
 
@@ -882,14 +862,9 @@ def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: 
     Cc = heads * hd
     out = Var(ops.attn_temporal(qkv.v, B, F, S, heads, hd))
 
-    def bwd():
-        dy, out.g = out.g, None
-        if dy is None:
-            return
-        if F == 1:                                   # one frame (the spatial-loss pass): softmax over one key is 1, out = V -> dV = dO, dQ = dK = 0
-            dqkv = torch.zeros_like(qkv.v)
-            dqkv[:, 2 * Cc:].copy_(dy)
-            _acc(qkv, dqkv)
+    def bwd(dy):
+        if F == 1:                                   # one frame (the spatial-loss pass)
+            _acc(qkv, _one_key_backward(qkv.v, dy, Cc))
             return
         if FLASH_BACKWARD and F <= TEMPORAL_FLASH_FRAMES and hd in (64, 128):
             dqkv = torch.empty_like(qkv.v)
@@ -899,5 +874,5 @@ def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: 
             return
         _acc(qkv, _attention_backward(qkv.v, dy, Cc, heads, hd, F, S, (B, F * S, S, 1), 1))
 
-    tape.record(bwd)
+    tape.op(out, bwd)
     return out

@@ -248,6 +248,99 @@ def test_elementwise_backward_kernels(dev, AD):
     assert torch.equal(z.float().cpu(), want)
 
 
+@pytest.fixture(scope="module")
+def blend_case():
+    """The AlphaBlender shapes of ``test_elementwise_backward_kernels`` (3840 elements: 15 blocks of the weight-gradient reduction,
+    mix 0.3) and the gradients of ``alpha a + (1 - alpha) b`` under autograd."""
+    a, b, g = h16(60, 64, seed=23), h16(60, 64, seed=24), h16(60, 64, seed=25)
+    mr, ar, br_ = torch.tensor([0.3], requires_grad=True), a.float().requires_grad_(True), b.float().requires_grad_(True)
+    al = torch.sigmoid(mr)
+    y = al * ar + (1 - al) * br_
+    y.backward(g.float())
+    return a, b, g, y.detach(), ar.grad, br_.grad, mr.grad
+
+
+def _forbidden(*args, **kw):
+    raise AssertionError("must not be called in this mode")
+
+
+def test_blend_with_the_weight_in_device_memory(dev, AD, blend_case, monkeypatch):
+    """``device_scalars`` (what ``use_graph=True`` runs): pt_lerp_f16_dev / pt_dot_diff_dev / pt_scale_f16_dev read sigmoid(mix) from
+    ``ParamStore.alphas``; the host never fetches the scalar.  Tolerances: those of the host mode above."""
+    a, b, g, y, da, db, dm = blend_case
+    P = AD.ParamStore({"m": torch.tensor([0.3])}, dev)
+    P.device_scalars = True
+    P.refresh_alphas()
+    monkeypatch.setattr(P, "scalar", _forbidden)
+    tape = AD.Tape()
+    av, bv = AD.Var(a.to(dev)), AD.Var(b.to(dev))
+    o = AD.blend(tape, av, bv, AD.Mix(P, "m"))
+    o.g = g.to(dev)
+    tape.backward()
+    got = rel(o.v, y), rel(av.g, da), rel(bv.g, db), rel(P.gradient("m"), dm)
+    print("blend, device scalars: forward %.2e, da %.2e, db %.2e, dmix %.2e" % got)
+    assert got[0] < 6e-4 and got[1] < 6e-4 and got[2] < 6e-4 and got[3] < 1e-3
+    assert o.g is None
+
+
+def test_blend_over_a_frozen_store(dev, AD, blend_case, monkeypatch):
+    """The frozen U-Net's AlphaBlender: data gradients only - no weight-gradient launch, ``gradient`` never asked for."""
+    from posetraj_amd import hip
+    a, b, g, y, da, db, _ = blend_case
+    P = AD.FrozenParams({"m": torch.tensor([0.3])}, dev)
+    monkeypatch.setattr(P, "gradient", _forbidden)
+    real, launched = hip.checked(), []
+
+    class Recording:
+        def __getattr__(self, name):
+            launched.append(name)
+            return getattr(real, name)
+
+    monkeypatch.setattr(hip, "checked", lambda: Recording())
+    tape = AD.Tape()
+    av, bv = AD.Var(a.to(dev)), AD.Var(b.to(dev))
+    o = AD.blend(tape, av, bv, AD.Mix(P, "m"))
+    o.g = g.to(dev)
+    tape.backward()
+    got = rel(o.v, y), rel(av.g, da), rel(bv.g, db)
+    print("blend, frozen store: forward %.2e, da %.2e, db %.2e; launches %s" % (got + (launched,)))
+    assert got[0] < 6e-4 and got[1] < 6e-4 and got[2] < 6e-4
+    assert "pt_lerp_f16" in launched and not any(n.startswith("pt_dot_diff") or n.endswith("_dev") for n in launched)
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_rows_backward_and_add_rows(dev, AD, shared):
+    """``rows``' backward - at once, and deferred then joined by ``add_rows`` - adds the gradient into rows ``r0:r1`` of ``x.g``: of a
+    zero fill when there is none yet, else of a CLONE - the tensor that was there is also another variable's gradient and keeps its
+    values.  Into zeros the sum is exact; onto a gradient it is one fp16 rounding of a sum of two fp16 numbers: 5e-4; the rows outside
+    the slice are exact."""
+    x, dy, g0 = h16(6 * 8, 16, seed=70).to(dev), h16(8, 16, seed=71).to(dev), h16(6 * 8, 16, seed=72).to(dev)
+    r0, r1 = 16, 24
+    want = g0.float() if shared else torch.zeros(48, 16, device=dev)
+    want[r0:r1] += dy.float()
+    kept = g0.clone()
+    for defer in (None, []):
+        tape = AD.Tape()
+        xv, other = AD.Var(x), AD.Var(x)
+        if shared:
+            xv.g = other.g = g0
+        o = AD.rows(tape, xv, r0, r1, defer=defer)
+        assert o.v.data_ptr() == x[r0:r1].data_ptr()
+        o.g = dy
+        tape.backward()
+        if defer is not None:
+            assert xv.g is (g0 if shared else None) and len(defer) == 1 and defer[0][:3] == (xv, r0, r1) and defer[0][3] is dy
+            AD.add_rows(*defer[0])
+        assert xv.g is not g0 and xv.g.shape == x.shape
+        assert rel(xv.g[r0:r1], want[r0:r1]) < 5e-4 if shared else torch.equal(xv.g[r0:r1], dy)
+        assert torch.equal(xv.g[:r0].float(), want[:r0]) and torch.equal(xv.g[r1:].float(), want[r1:])
+        if shared:
+            assert other.g is g0 and torch.equal(g0, kept)      # never modified in place
+    quiet = AD.Var(x, need=False)
+    AD.add_rows(quiet, r0, r1, dy)
+    assert quiet.g is None
+
+
 def test_edm_loss_backward_adamw_and_norm(dev):
     from posetraj_amd import hip, ops
     L, st = hip.lib(), ops._stream()

@@ -107,7 +107,7 @@ def test_product_calls_pass_as_many_arguments_as_the_header_declares():
                     skipped.append((f, node.lineno))
                     continue
                 assert len(node.args) == len(hip.SIGNATURES[node.func.attr][1]), (f, node.lineno, node.func.attr)
-    assert sites >= 75 and len(skipped) <= 2, (sites, skipped)
+    assert sites >= 74 and len(skipped) <= 2, (sites, skipped)         # (the floor is the census: every call site there is)
 
 
 def test_checked_handle_raises_where_the_raw_one_returns(lib):
