@@ -53,6 +53,16 @@ int pt_set_zero_page(const void* dev_zeros_256B);
  * the image (F, H*W)).  Hout / Wout are taken as given: rows / columns of taps beyond the input read zeros, so
  * Downsample2D(padding=0)'s F.pad(0,1,0,1) + stride-2 convolution is pad_h = pad_w = 0 with
  * Hout = (Hin + 1 - 3) / 2 + 1.
+ * upsample2x: 0 none; 1 the source is read as its nearest-2x upsampled image (Hout x Wout relate to 2 Hin x 2 Win; any kernel,
+ *   any epilogue); 2 "folded" - the same layer for a 3 x 3, padding-1 kernel as four 2 x 2 convolutions on the low-resolution
+ *   source, one per output parity class par = 2 py + px, on weights summed at pack time (packing.pack_conv2d_upfold): output
+ *   pixel (2 i + py, 2 j + px) takes tap (a, b) from source pixel (i - (1 - py) + a, j - (1 - px) + b), zeros outside.  The
+ *   caller passes KH = KW = 2, stride = 1, Hout = 2 Hin, Wout = 2 Win, M = Nimg * Hout * Wout and K = 4 C0; `w` holds the four
+ *   [Npad, Kpad] images stacked by par (image par starts at row par * Npad), `bias` is shared; pad_h / pad_w are ignored.
+ *   Rows are computed class by class and written to their place in the ordinary [Nimg, Hout, Wout, N] output.  K drops from
+ *   9 C0 to 4 C0.  Mode 2 serves Upsample2D's convolution only and refuses everything that layer does not use: x1, res,
+ *   res_lo, vec, blend, out_lo, out_f32, act != 0, cs_cols, C0 % 64 != 0 or a padded K; it never runs split-K.  Results
+ *   differ from mode 1 by the rounding of the folded weights (summed in fp32, rounded to fp16 once).
  * vec_mode: 0 none; 1 vidx = m / vG (per frame / per clip row vectors); 2 the batch-interleaved index of the
  *   temporal cross-attention context (models/modified_svd.py:152-159): vidx = ((m / vFS) * vS + m % vS) % vB.
  * Replaces: nn.Conv2d / nn.Conv3d((3,1,1)) / nn.Linear dispatches of diffusers' ResnetBlock2D,

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .packing import pack_conv2d, pack_conv_t3, pack_linear, vec16
+from .packing import pack_conv2d, pack_conv2d_upfold, pack_conv_t3, pack_linear, vec16
 
 HEAD_DIMS = (64, 128)
 # feed-forward intermediates larger than this are produced and consumed in row chunks (TransformerSpatioTemporalModel._feed_forward)
@@ -321,7 +321,8 @@ class UpBlock:
             j += 1
         self.up = None
         if p + "upsamplers.0.conv.weight" in sd:
-            self.up = pack_conv2d(sd[p + "upsamplers.0.conv.weight"], sd[p + "upsamplers.0.conv.bias"], device)
+            # nearest-2x + 3 x 3 conv as four 2 x 2 convs on folded weights: 4/9 of the products (packing.pack_conv2d_upfold)
+            self.up = pack_conv2d_upfold(sd[p + "upsamplers.0.conv.weight"], sd[p + "upsamplers.0.conv.bias"], device)
 
     def run(self, ctx, x, skips: List[torch.Tensor]):
         skips = list(skips)

@@ -16,6 +16,10 @@
 //   are staged with 16-byte LDS-DMA (global_load_lds_dwordx4) straight from a per-lane gathered source address:
 //   im2col, zero padding (padded taps read a zero page), the 2-source skip concatenation and the nearest-2x
 //   upsampling all live in that address computation and cost no extra pass over HBM.
+//   Folded upsampler (pt_igemm_params.upsample2x == 2): nearest-2x + 3 x 3 conv is four 2 x 2 convs on the low-resolution
+//   source, one per output parity class, on weights summed at pack time - K = 4 C instead of 9 C.  The M tiles are four
+//   class-local runs (class_of); the class picks the origin shift of the gather (row_origin), its weight image and the
+//   output row of every stored row (igemm_tail: out_row).  No K loop knows about it.
 //   LDS image: rows of 128 B (64 halfs), the eight 16-B chunks of row r XOR-swizzled by (r >> 1) & 7 on the
 //   SOURCE side (the DMA destination is lane-linear), undone in the ds_read_b128 address: conflict-free reads.
 //   Two LDS stages; the DMA of tile k+1 is in flight while the MFMAs of tile k run.
@@ -37,19 +41,31 @@ __device__ __forceinline__ void tile_of(const KParams& kp, int bid, int& tile_m,
     tile_m = first_m + within % gm; tile_n = within / gm;
 }
 
+// Folded upsampler (upsample2x == 2): the M tiles are four runs of kp.class_tiles, one per output parity class par = 2 py + px;
+// kp.p.M is the row count of ONE class, so the ragged last tile of every class is masked by the m < p.M tests there already are.
+// Wave-uniform.  Returns par (0 for every other launch) and makes tile_m class-local.
+__device__ __forceinline__ int class_of(const KParams& kp, int& tile_m) {
+    if (!kp.class_tiles) return 0;
+    const int par = tile_m / kp.class_tiles;
+    tile_m -= par * kp.class_tiles;
+    return par;
+}
+
 // Output row m -> iyx = (iy0 << 16 | ix0 & 0xffff), the top-left tap of its pixel, and pix0, the pixel base of its image.
 // One-column kernels (kp.foldx) fold the output column into pix0 and keep ix0 = 0.
-__device__ __forceinline__ void row_origin(const KParams& kp, int m, int& iyx, int& pix0) {
+// Folded upsampler: kp.p holds the class geometry (Hout x Wout = Hin x Win) and the origin shift of class `par` is (1 - py, 1 - px).
+__device__ __forceinline__ void row_origin(const KParams& kp, int par, int m, int& iyx, int& pix0) {
     const pt_igemm_params& p = kp.p;
     if (m < p.M) {
         const int HWo = p.Hout * p.Wout;
+        const int pad_h = kp.class_tiles ? 1 - (par >> 1) : p.pad_h, pad_w = kp.class_tiles ? 1 - (par & 1) : p.pad_w;
         int img = m, oy = 0, ox = 0;                         // linear layers (one-pixel images) skip the two divisions
         if (HWo != 1) {
             img = m / HWo;
             const int rem = m - img * HWo;
             oy = rem / p.Wout; ox = rem - oy * p.Wout;
         }
-        iyx = ((oy * p.stride - p.pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - p.pad_w) & 0xffff);
+        iyx = ((oy * p.stride - pad_h) << 16) | ((kp.foldx ? 0 : ox * p.stride - pad_w) & 0xffff);
         pix0 = img * p.Hin * p.Win + (kp.foldx ? ox : 0);
     } else {
         iyx = (int)0xC0000000; pix0 = 0;                     // iy0 = -16384: every tap is out of bounds
@@ -57,12 +73,12 @@ __device__ __forceinline__ void row_origin(const KParams& kp, int m, int& iyx, i
 }
 
 // Where tap (ky, kx) of a decoded row reads channel `cofs` of `src` (pitch ld): bounds test in the (upsampled) input extent,
-// nearest-2x upsampling as a coordinate shift, and the zero page `zsrc` for padded taps (ok = false).
+// nearest-2x upsampling (mode 1) as a coordinate shift, and the zero page `zsrc` for padded taps (ok = false).
 __device__ __forceinline__ const f16* tap_source(const pt_igemm_params& p, int iyx, int pix0, int ky, int kx, const f16* src, int ld,
                                                  int cofs, const f16* zsrc, int Hlim, int Wlim, bool& ok) {
     int iy = (iyx >> 16) + ky, ix = (int)(short)(iyx & 0xffff) + kx;
     ok = ok && (unsigned)iy < (unsigned)Hlim && (unsigned)ix < (unsigned)Wlim;
-    if (p.upsample2x) { iy >>= 1; ix >>= 1; }
+    if (p.upsample2x == 1) { iy >>= 1; ix >>= 1; }
     return ok ? src + ((size_t)(pix0 + iy * p.Win + ix) * ld + cofs) : zsrc;
 }
 
@@ -124,6 +140,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     const int bid = pt_xcd_remap(blockIdx.x, gridDim.x);
     int tile_m, tile_n;
     tile_of(kp, bid, tile_m, tile_n);
+    const int par = class_of(kp, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
@@ -133,8 +150,8 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     const int Ctot = p.C0 + p.C1;
     int iyx[CF::A_SLOTS], pix0[CF::A_SLOTS];
 #pragma unroll
-    for (int i = 0; i < CF::A_SLOTS; ++i) row_origin(kp, m0 + (t >> 3) + (NT / 8) * i, iyx[i], pix0[i]);
-    const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
+    for (int i = 0; i < CF::A_SLOTS; ++i) row_origin(kp, par, m0 + (t >> 3) + (NT / 8) * i, iyx[i], pix0[i]);
+    const int Hlim = p.upsample2x == 1 ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x == 1 ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
     int woff[CF::B_SLOTS];
 #pragma unroll
@@ -143,7 +160,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
         if (wrow >= kp.npad) wrow = kp.npad - 1;             // columns >= N are never stored; keep the read in bounds
         woff[i] = wrow * p.Kpad + csrc * 8;
     }
-    const f16* wbase = (const f16*)p.w;
+    const f16* wbase = (const f16*)p.w + (size_t)par * kp.npad * p.Kpad;   // (the folded upsampler's weight image of this class)
     const int nk = p.Kpad / BK;
 
     const f16* aptr[CF::A_SLOTS];                            // FAST path: channel-aligned K tiles (retarget)
@@ -241,7 +258,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     }
     compute(cur);
 
-    igemm_epilogue<CF, V_RT>(kp, acc, smem, m0, n0, wave, lane);
+    igemm_epilogue<CF, V_RT, true>(kp, acc, smem, m0, n0, wave, lane, par);
 }
 
 // ============================================================================ 256 x 256, 8-phase ping-pong main loop
@@ -276,6 +293,8 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
     const int bid = pt_xcd_remap(blockIdx.x, gridDim.x);
     int tile_m, tile_n;
     tile_of(kp, bid, tile_m, tile_n);
+    int par = 0;                                             // (the folded upsampler has no side input: only the V_P0 instance serves it)
+    if constexpr (VAR == V_P0) par = class_of(kp, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
@@ -287,9 +306,9 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int h = a >> 1, sl = a & 1;
-        row_origin(kp, m0 + ((t >> 8) + 2 * sl) * 64 + h * 32 + ((t >> 3) & 31), iyx[a], pix0[a]);
+        row_origin(kp, par, m0 + ((t >> 8) + 2 * sl) * 64 + h * 32 + ((t >> 3) & 31), iyx[a], pix0[a]);
     }
-    const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
+    const int Hlim = p.upsample2x == 1 ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x == 1 ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
     int woff[4];
 #pragma unroll
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         if (wrow >= kp.npad) wrow = kp.npad - 1;
         woff[a] = wrow * p.Kpad + csrc * 8;
     }
-    const f16* wbase = (const f16*)p.w;
+    const f16* wbase = (const f16*)p.w + (size_t)par * kp.npad * p.Kpad;   // (the folded upsampler's weight image of this class)
     const int nk = p.Kpad / BK;
 
     const f16* aptr[4];
@@ -418,7 +437,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         // loop, where every register is taken: make the lane id opaque here
         int lane_t = lane;
         asm volatile("" : "+v"(lane_t));
-        igemm_epilogue<CF, VAR>(kp, acc, smem, m0, n0, wave, lane_t);
+        igemm_epilogue<CF, VAR, VAR == V_P0>(kp, acc, smem, m0, n0, wave, lane_t, par);
     }
     ig_stamp(kp, wave, lane, 3);
     __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
@@ -454,6 +473,8 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     const int split = bid_all / ntiles, bid = bid_all - split * ntiles;
     int tile_m, tile_n;
     tile_of(kp, bid, tile_m, tile_n);
+    int par = 0;                                             // (the folded upsampler has no side input: only the V_P0 instance serves it)
+    if constexpr (VAR == V_P0) par = class_of(kp, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f16x4 b4[TN];
     bias_issue<CF>(kp, n0, wave, lane, b4);
@@ -463,8 +484,8 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     const int csrc = lds_src_chunk(t);
     int iyx[4], pix0[4];
 #pragma unroll
-    for (int a = 0; a < 4; ++a) row_origin(kp, m0 + a * 64 + (t >> 3), iyx[a], pix0[a]);
-    const int Hlim = p.upsample2x ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x ? 2 * p.Win : p.Win;
+    for (int a = 0; a < 4; ++a) row_origin(kp, par, m0 + a * 64 + (t >> 3), iyx[a], pix0[a]);
+    const int Hlim = p.upsample2x == 1 ? 2 * p.Hin : p.Hin, Wlim = p.upsample2x == 1 ? 2 * p.Win : p.Win;
     const f16* zsrc = kp.zeros + (lane & 7) * 8;
     // weight row of this thread's chunk in piece j: n0 + wc*160 + (2j + f)*16 + r with (wc, f, r) from LDS row t >> 3
     const int wrow0 = n0 + lds_wpiece_row(t >> 3);
@@ -475,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
         if (wrow >= kp.npad) wrow = kp.npad - 1;
         woff[j] = wrow * p.Kpad + csrc * 8;
     }
-    const f16* wbase = (const f16*)p.w;
+    const f16* wbase = (const f16*)p.w + (size_t)par * kp.npad * p.Kpad;   // (the folded upsampler's weight image of this class)
     const int nk_all = p.Kpad / BK;
     const int per_split = (nk_all + kp.splits - 1) / kp.splits;
     const int kbeg = split * per_split;                      // this workgroup's K tiles: [kbeg, kbeg + nk)
@@ -624,7 +645,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     } else {
         int lane_t = lane;                                   // (opaque: keeps the tail's lane-derived values below the K loop)
         asm volatile("" : "+v"(lane_t));
-        igemm_epilogue<CF, VAR>(kp, acc, smem, m0, n0, wave, lane_t);
+        igemm_epilogue<CF, VAR, VAR == V_P0>(kp, acc, smem, m0, n0, wave, lane_t, par);
         ig_stamp(kp, wave, lane, 3);
         __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));             // no LDS-DMA may outlive the wave
     }
@@ -718,7 +739,8 @@ using CfgN32 = Cfg<4, 1, 4, 2>;                // 256 x 32: 4 waves of 64 x 32 -
 // K tile + epilogue), with the per-configuration constants read off the s_memtime stamps / sweeps in
 // profiles/r01/igemm_stamps_v14.txt and igemm_cfg_sweep_v14.txt.  `fast` = channel-aligned K tiles (the pipelined
 // 256 x 256 and 256 x 320 kernels need it).
-int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast) {
+// `classes`: the M rows are that many equal runs tiled separately (4 parity classes of the folded upsampler, else 1).
+int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast, int classes) {
     struct Opt { int bm, bn, slots; double pro, loop, epi, epi_geglu, epi_side; };
     static const Opt pipelined[5] = {
         {256, 256, 256, 5000, 2650, 10500, 8700, 4000},      // 8-phase ping-pong
@@ -737,7 +759,7 @@ int choose_cfg(int M, int N, int nk, int act, bool has_side, bool fast) {
         if (i == 1 && act == 1) continue;                    // odd TN: no GEGLU pairs
         if (i == 3 && !fast) continue;
         const Opt& o = pipelined[i];
-        const double tiles = (double)((M + o.bm - 1) / o.bm) * ((N + o.bn - 1) / o.bn);
+        const double tiles = (double)(classes * ((M / classes + o.bm - 1) / o.bm)) * ((N + o.bn - 1) / o.bn);
         const double rounds = (double)(long long)((tiles + o.slots - 1) / o.slots);
         const double loop = (i == 0 && !fast) ? 3400 : o.loop;                 // the plain 256 x 256 loop
         const double tile = o.pro + nk * loop + (act == 1 ? o.epi_geglu : o.epi) + (has_side ? o.epi_side : 0);
@@ -841,6 +863,7 @@ extern "C" int pt_igemm_set_tuning(int32_t group_m, int32_t ablation) {
 // (K < 3072) stay un-split: there the 128-row tiles already give one workgroup per CU and the two launches + fp32 slab round
 // trip of split-K lose to them (2520 x 1280 x 1280: 38.7 us split, 19.7 us on 128 x 128 tiles; tools/micro/igemm_cfg_sweep.py).
 static int plan_splits(const pt_igemm_params& p, bool fast, bool vec_ok) {
+    if (p.upsample2x == 2) return 1;                         // the folded upsampler scatters rows in the tail; the reducer does not
     if (!fast || !vec_ok || p.act == 1 || p.N % 8 != 0) return 1;
     const int tiles = ((p.M + 255) / 256) * ((p.N + 319) / 320), nk = p.Kpad / BK;
     if (tiles > 128 || nk < 48) return 1;
@@ -864,7 +887,7 @@ namespace {
 // touches no device, so pt_igemm_splitk_ws_bytes and pt_igemm_plan ask it too.
 struct Plan {
     bool fast, foldx, vec_ok;
-    int cfg, splits, gm, tiles_m, tiles_n;
+    int cfg, splits, gm, tiles_m, tiles_n, class_tiles;
     int64_t ws_bytes;
 };
 
@@ -885,7 +908,19 @@ int plan(const pt_igemm_params& p, Plan& pl) {
     PT_CHECK((long long)p.Hout * p.stride + p.KH < 32000 && (pl.foldx || (long long)p.Wout * p.stride + p.KW < 32000),
              "pt_igemm_f16: output extent %d x %d too large (a linear layer is Nimg = M, H = W = 1)", p.Hout, p.Wout);
     PT_CHECK((long long)p.Nimg * p.Hin * p.Win < (1ll << 31), "pt_igemm_f16: more than 2^31 input pixels");
+    PT_CHECK(p.upsample2x >= 0 && p.upsample2x <= 2, "pt_igemm_f16: upsample2x=%d (0 none, 1 nearest-2x source, 2 folded nearest-2x)", p.upsample2x);
     PT_CHECK(!(p.upsample2x && p.stride != 1), "pt_igemm_f16: upsample2x needs stride 1");
+    const bool fold = p.upsample2x == 2;
+    if (fold) {                                              // the upsampler of the up blocks and nothing else
+        PT_CHECK(p.KH == 2 && p.KW == 2 && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win,
+                 "pt_igemm_f16: folded upsample (upsample2x=2) needs KH = KW = 2 and Hout x Wout = 2 Hin x 2 Win (got %d x %d taps, %d x %d -> %d x %d)",
+                 p.KH, p.KW, p.Hin, p.Win, p.Hout, p.Wout);
+        PT_CHECK(!p.x1, "pt_igemm_f16: folded upsample takes one source (x1 must be NULL)");
+        PT_CHECK(!p.res && !p.res_lo && !p.vec && !p.blend, "pt_igemm_f16: folded upsample takes no side input (res / res_lo / vec / blend)");
+        PT_CHECK(!p.out_lo && !p.out_f32, "pt_igemm_f16: folded upsample writes one fp16 output (no out_lo / out_f32)");
+        PT_CHECK(p.act == 0 && p.cs_cols == 0, "pt_igemm_f16: folded upsample has no activation and no column scale (act=%d cs_cols=%d)", p.act, p.cs_cols);
+        PT_CHECK(p.C0 % BK == 0 && p.Kpad == p.K, "pt_igemm_f16: folded upsample needs C0 %% 64 == 0 and an unpadded K (C0=%d K=%d Kpad=%d)", p.C0, p.K, p.Kpad);
+    }
     PT_CHECK(p.act == 0 || p.act == 2 || (p.act == 1 && p.N % 32 == 0), "pt_igemm_f16: act must be 0, 1 (GEGLU, N %% 32 == 0) or 2 (SiLU)");
     PT_CHECK(p.vec_mode == 0 || p.vec, "pt_igemm_f16: vec_mode without vec");
     PT_CHECK(!(p.res_post && !p.res), "pt_igemm_f16: res_post without res");
@@ -898,7 +933,7 @@ int plan(const pt_igemm_params& p, Plan& pl) {
                 (!p.vec || (p.ldv % 8 == 0 && al16(p.vec))) && (!p.blend || (p.ldb % 8 == 0 && al16(p.blend)));
     pl.fast = (Ctot % BK == 0) && (p.C0 % BK == 0) && (p.Kpad == p.K);
     const int force = g_force_cfg;
-    int cfg = force >= 0 ? force : choose_cfg(p.M, p.N, p.Kpad / BK, p.act, p.res || p.blend, pl.fast);
+    int cfg = force >= 0 ? force : choose_cfg(p.M, p.N, p.Kpad / BK, p.act, p.res || p.blend, pl.fast, fold ? 4 : 1);
     const int want = (force < 0 || force == 3) ? plan_splits(p, pl.fast, pl.vec_ok) : 1;
     pl.ws_bytes = want > 1 ? (int64_t)want * p.M * p.N * 4 : 0;
     pl.splits = (want > 1 && p.splitk_ws && p.splitk_ws_bytes >= pl.ws_bytes) ? want : 1;   // else no workspace offered
@@ -909,7 +944,8 @@ int plan(const pt_igemm_params& p, Plan& pl) {
     PT_CHECK(!(cfg == 1 && p.act == 1), "pt_igemm_f16: the 128x320 configuration does not support GEGLU");
     pl.cfg = cfg;
     const int bm = (cfg == 0 || cfg == 3 || cfg == 5) ? 256 : 128, bn = cfg == 0 ? 256 : (cfg == 2 ? 128 : (cfg == 4 ? 160 : (cfg == 5 ? 32 : 320)));
-    pl.tiles_m = (p.M + bm - 1) / bm;
+    pl.class_tiles = fold ? (p.M / 4 + bm - 1) / bm : 0;   // M = 4 class_rows: each parity class is tiled on its own
+    pl.tiles_m = fold ? 4 * pl.class_tiles : (p.M + bm - 1) / bm;
     pl.tiles_n = (p.N + bn - 1) / bn;
     PT_CHECK((long long)pl.tiles_m * pl.tiles_n < (1ll << 31), "pt_igemm_f16: grid too large");
     const double in_px = p.upsample2x ? p.M / 4.0 : (double)p.M * p.stride * p.stride;
@@ -948,6 +984,10 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
     kp.foldx = pl.foldx ? 1 : 0;
     kp.vec_ok = pl.vec_ok;
     kp.tiles_m = pl.tiles_m;
+    kp.class_tiles = pl.class_tiles;
+    if (pl.class_tiles) {                                    // the kernels see ONE class: its rows and its extent (Hin x Win pixels)
+        kp.p.M = p.M / 4; kp.p.Hout = p.Hin; kp.p.Wout = p.Win;
+    }
     kp.tiles_n = pl.tiles_n;
     kp.gm = pl.gm;
     kp.ws = nullptr; kp.splits = 1;

@@ -15,6 +15,8 @@ struct KParams {
     pt_igemm_params p;
     const f16* zeros;
     int tiles_m, tiles_n;
+    int class_tiles;  // folded upsampler (p.upsample2x == 2): M tiles per output parity class - tiles_m = 4 class_tiles, p.M = rows of one
+                      // class, p.Hout x p.Wout = the class extent Hin x Win; 0 for every other launch
     int npad;       // rows of the packed weight image
     int vec_ok;     // 16-byte epilogue path allowed
     int gm;         // M tiles per rasterisation group (see the kernel's tile-order comment)
@@ -148,9 +150,9 @@ __device__ __forceinline__ void bias_init(const f16x4 (&b4)[CF::TN], f32x4 (&acc
 // normalise it read `out` alone (exactly the fp16 tensor), the epilogue that adds it as a residual reads res + res_lo
 // (side-input kind 4).  The one-rounding-per-block random walk of the stream - 0.98e-3 of the U-Net's 1.08e-3 rel-L2
 // (profiles/r02/parity_ladder*.txt) - drops to 2^-22 per store.
-template <class CF, int NTL, bool GEGLU, int NS, bool WIDE>
+template <class CF, int NTL, bool GEGLU, int NS, bool WIDE, bool FOLD = false>
 __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::TN][CF::TM], char* smem,
-                                           int mrow0, int wcol0, int Nout, int wave, int lane) {
+                                           int mrow0, int wcol0, int Nout, int wave, int lane, int par) {
     // (GEGLU chunks half as tall - the stores of chunk c under the GELU arithmetic of chunk c + 1 - measured +-0.5 % on both
     // pipelined kernels: profiles/r03/igemm_geglu_chunk_height_ab.txt)
     using TG = TailGeom<CF::WM * CF::WN, CF::TM, NTL, CF::EPI_CAP>;
@@ -243,12 +245,16 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
         }
         return o;
     };
+    // Folded upsampler: in-class row mc = (img * Hin + i) * Win + j of parity class (py, px) is pixel (2 i + py, 2 j + px) of the
+    // [Nimg, 2 Hin, 2 Win] output: row (mc / Win) * 4 Win + py * 2 Win + 2 (mc % Win) + px = 2 (mc + (mc / Win) Win) + py * 2 Win + px.
+    constexpr bool FOLDABLE = FOLD && !GEGLU && NS == 0 && !WIDE;   // (no side input, no activation, one output; FOLD: igemm.hip's kernels only)
+    auto out_row = [&](int m) { return FOLDABLE && kp.class_tiles ? 2 * (m + m / p.Win * p.Win) + (par >> 1) * 2 * p.Win + (par & 1) : m; };
     auto store_row = [&](int rc, int g, const f16x8& o, const f16x8& lo8) {
         int r, c8;
         slot(g, r, c8);
         const int m = mrow0 + rc * RH + r;
         if (lane_live && r < RH && m < p.M && !(kp.dbg & 1)) {
-            const size_t off = (size_t)m * p.ldo + wcol0 + c8;
+            const size_t off = (size_t)out_row(m) * p.ldo + wcol0 + c8;
             *(f16x8*)(out + off) = o;
             if constexpr (WIDE) *(f16x8*)(out_lo + off) = lo8;
         }
@@ -319,6 +325,7 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                 const int m = mc0 + r;
                 if (m >= p.M) break;
                 const float* e = E + r * ELD + (col0 - wcol0);
+                const size_t orow = (size_t)out_row(m);      // (side inputs, refused for the folded upsampler, stay on m)
                 for (int j = 0; j < 8 && col0 + j < Nout; ++j) {
                     float x = e[j];
                     float rs = res ? (float)res[(size_t)m * p.ldr + col0 + j] : 0.f;
@@ -328,11 +335,11 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                     if (blend) x = alpha * (float)blend[(size_t)m * p.ldb + col0 + j] + (1.0f - alpha) * x;
                     x *= col_scale(col0);
                     if (res && res_post) x += rs;
-                    if (p.out_f32) ((float*)p.out)[(size_t)m * p.ldo + col0 + j] = x;
+                    if (p.out_f32) ((float*)p.out)[orow * p.ldo + col0 + j] = x;
                     else {
                         const f16 o = (f16)x;
-                        out[(size_t)m * p.ldo + col0 + j] = o;
-                        if (out_lo) out_lo[(size_t)m * p.ldo + col0 + j] = (f16)(x - (float)o);
+                        out[orow * p.ldo + col0 + j] = o;
+                        if (out_lo) out_lo[orow * p.ldo + col0 + j] = (f16)(x - (float)o);
                     }
                 }
             }
@@ -365,9 +372,9 @@ __device__ __forceinline__ int tail_variant_dev(const pt_igemm_params& p) {
     return (p.out_lo ? V_W0 : V_P0) + nside;
 }
 
-template <class CF, int VAR>
+template <class CF, int VAR, bool FOLD = false>
 __device__ __forceinline__ void igemm_epilogue(const KParams& kp, f32x4 (&acc)[CF::TN][CF::TM], char* smem,
-                                               int m0, int n0, int wave, int lane) {
+                                               int m0, int n0, int wave, int lane, int par = 0) {
     constexpr int TM = CF::TM, TN = CF::TN;
     const pt_igemm_params& p = kp.p;
     const int wr = wave / CF::WN, wc = wave % CF::WN;
@@ -385,12 +392,12 @@ __device__ __forceinline__ void igemm_epilogue(const KParams& kp, f32x4 (&acc)[C
     const int mrow0 = m0 + wr * TM * 16;
     const int var = VAR == V_RT ? tail_variant_dev(p) : VAR;
     if constexpr (TN % 2 == 0 && (VAR == V_RT || G)) {
-        if (var == V_G0)  { igemm_tail<CF, TN / 2, true, 0, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane); return; }
-        if (var == V_GEW) { igemm_tail<CF, TN / 2, true, 3, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane); return; }
+        if (var == V_G0)  { igemm_tail<CF, TN / 2, true, 0, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
+        if (var == V_GEW) { igemm_tail<CF, TN / 2, true, 3, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
     }
 #define PT_TAIL_CASE(V, NS_, WIDE_)                                                                                \
     if constexpr (VAR == V_RT || VAR == V)                                                                         \
-        if (var == V) { igemm_tail<CF, TN, false, NS_, WIDE_>(kp, acc, smem, mrow0, wcol0, p.N, wave, lane); return; }
+        if (var == V) { igemm_tail<CF, TN, false, NS_, WIDE_, FOLD>(kp, acc, smem, mrow0, wcol0, p.N, wave, lane, par); return; }
     PT_TAIL_CASE(V_P0, 0, false)
     PT_TAIL_CASE(V_P1, 1, false)
     PT_TAIL_CASE(V_P2, 2, false)

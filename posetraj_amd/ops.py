@@ -100,6 +100,7 @@ class Packed:
     cin: int = 0          # channels per tap (after padding to a multiple of 8)
     geglu: bool = False
     silu: bool = False
+    upfold: bool = False  # packing.pack_conv2d_upfold: four parity-class images stacked by rows (pt_igemm_params.upsample2x == 2)
 
     @property
     def Kpad(self):
@@ -108,6 +109,26 @@ class Packed:
     @property
     def n_out(self):
         return self.N // 2 if self.geglu else self.N
+
+
+_fold_ok: Optional[bool] = None
+
+
+def _need_fold_mode() -> None:
+    """PT_ABI_VERSION did not change with ``pt_igemm_params.upsample2x == 2``, so a library built before the mode passes the version
+    check and would read 2 as "gathered upsample" - wrong output, not an error.  Probe once (host only, pt_igemm_plan touches no
+    device): a library that knows the mode refuses ``upsample2x = 3``, an older one takes any non-zero value."""
+    global _fold_ok
+    if _fold_ok is None:
+        p = hip.IgemmParams()
+        p.x0 = p.w = p.out = 256                      # never dereferenced by the plan
+        p.C0, p.ld0, p.ldo, p.N = 64, 64, 64, 64
+        p.Nimg, p.Hin, p.Win, p.Hout, p.Wout = 1, 1, 1, 2, 2
+        p.KH, p.KW, p.stride, p.upsample2x = 2, 2, 1, 3
+        p.M, p.K, p.Kpad = 4, 256, 256
+        _fold_ok = hip.lib().pt_igemm_plan(C.byref(p), None, None, None) != 0
+    if not _fold_ok:
+        raise RuntimeError(f"posetraj_amd.igemm: {hip.LIB_PATH} predates the folded upsampler (pt_igemm_params.upsample2x == 2); rebuild it")
 
 
 def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, geom=None, upsample2x: bool = False,
@@ -140,9 +161,13 @@ def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, ge
         Hs, Ws = (2 * Hin, 2 * Win) if upsample2x else (Hin, Win)
         Hout = (Hs + 2 * pw.pad_h - pw.KH) // pw.stride + 1
         Wout = (Ws + 2 * pw.pad_w - pw.KW) // pw.stride + 1
+        if pw.upfold:                     # four 2 x 2 convolutions, one per output parity: the library scatters the rows
+            Hout, Wout = 2 * Hin, 2 * Win
         if out_hw is not None:
             Hout, Wout = int(out_hw[0]), int(out_hw[1])
     M = Nimg * Hout * Wout
+    if pw.upfold and not (upsample2x and geom is not None and out_hw is None):
+        raise RuntimeError("posetraj_amd.igemm: a folded upsampler pack (pack_conv2d_upfold) serves upsample2x=True convolutions only")
     if pw.cin != C0 + C1:
         raise RuntimeError(f"posetraj_amd.igemm: weight packed for {pw.cin} input channels, got {C0}+{C1}")
     n_out = pw.n_out
@@ -158,7 +183,10 @@ def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, ge
     p.ld1 = (x1.stride(-2) if x1 is not None else 0)
     p.Nimg, p.Hin, p.Win, p.Hout, p.Wout = Nimg, Hin, Win, Hout, Wout
     p.KH, p.KW, p.stride, p.pad_h, p.pad_w = pw.KH, pw.KW, pw.stride, pw.pad_h, pw.pad_w
-    p.upsample2x = 1 if upsample2x else 0
+    up_mode = (2 if pw.upfold else 1) if upsample2x else 0
+    if up_mode == 2:
+        _need_fold_mode()
+    p.upsample2x = up_mode
     p.M, p.N, p.K, p.Kpad = M, pw.N, pw.K, pw.Kpad
     p.w, p.bias = pw.w.data_ptr(), _ptr(pw.bias)
     p.out, p.ldo = out.data_ptr(), out.stride(0)
@@ -192,7 +220,7 @@ def igemm(x0: torch.Tensor, pw: Packed, *, x1: Optional[torch.Tensor] = None, ge
     if out_lo is not None:
         _attach_lo(out, out_lo)
     if Profiler.shapes is not None:
-        Profiler.shapes.append((M, pw.N, pw.K, pw.KH, pw.KW, pw.stride, int(upsample2x), C1, p.act,
+        Profiler.shapes.append((M, pw.N, pw.K, pw.KH, pw.KW, pw.stride, up_mode, C1, p.act,
                                 int(res is not None) + 2 * int(vec is not None) + 4 * int(blend is not None) +
                                 8 * int(res_lo is not None) + 16 * int(out_lo is not None)))
     return out

@@ -59,6 +59,33 @@ def pack_conv2d(w: torch.Tensor, bias: Optional[torch.Tensor], device, stride: i
                    KH=kh, KW=kw, stride=stride, pad_h=padding, pad_w=padding, cin=cip)
 
 
+# Nearest-2x upsampling followed by a 3 x 3, padding-1 convolution reads only a 2 x 2 neighbourhood of the low-resolution image;
+# which one depends on the parity (py, px) of the output pixel.  Output row parity p folds the three kernel rows into two taps:
+_UPFOLD_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # [p][a] -> the original ky (kx) summed into tap a
+
+
+def pack_conv2d_upfold(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> Packed:
+    """``Upsample2D``'s 3 x 3 convolution ``[Co, Ci, 3, 3]`` as four 2 x 2 convolutions on the low-resolution input, one per output
+    parity class ``par = 2 py + px`` (``pt_igemm_params.upsample2x == 2``): output pixel ``(2 i + py, 2 j + px)`` takes tap ``(a, b)``
+    from input ``(i - (1 - py) + a, j - (1 - px) + b)``.  The four ``[Npad, Kpad]`` images (K ordered a, b, ci) are stacked by ``par``;
+    the taps are summed in fp32 from whatever dtype the state dict holds and rounded to fp16 once.  The bias is shared."""
+    co, ci, kh, kw = w.shape
+    if (kh, kw) != (3, 3) or ci % 64:
+        raise ValueError(f"unsupported upsampler weight {tuple(w.shape)}: 3 x 3 with a multiple of 64 input channels")
+    w32 = w.detach().float().permute(0, 2, 3, 1)                               # [co, ky, kx, ci]
+    blocks = []
+    for par in range(4):
+        rows, cols = _UPFOLD_TAPS[par >> 1], _UPFOLD_TAPS[par & 1]
+        f = torch.stack([torch.stack([sum(w32[:, ky, kx] for ky in rows[a] for kx in cols[b]) for b in range(2)], dim=1)
+                         for a in range(2)], dim=1)                              # [co, a, b, ci]
+        blocks.append(_finish(f.reshape(co, 4 * ci), None, device).w)
+    b = None
+    if bias is not None:
+        b = torch.zeros((blocks[0].shape[0],), dtype=torch.float16, device=device)
+        b[:co] = bias.detach().to(device=device, dtype=torch.float16)
+    return Packed(w=torch.cat(blocks, dim=0), bias=b, N=co, K=4 * ci, KH=2, KW=2, stride=1, pad_h=0, pad_w=0, cin=ci, upfold=True)
+
+
 def pack_conv_t3(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> Packed:
     """Conv3d ``[Co, Ci, 3, 1, 1]`` (padding (1,0,0)) -> a (3 x 1) convolution over the image (H', W') = (F, H*W)."""
     co, ci, kt, kh, kw = w.shape
