@@ -100,6 +100,17 @@ def checkpoint(tape: Tape, fn: Callable[[Tape], Var]) -> Var:
 
 
 WGRAD_STREAM: Optional[torch.cuda.Stream] = None      # set by the trainer: weight gradients run beside the data gradients
+# Set by the trainer for the span of a step, from ``ParamStore.deterministic`` (``ControlNetTrainer(deterministic=True)``): every
+# reduction of the reverse pass that accumulates with atomics takes its two-stage ``ptd_`` form (include/posetraj_det.h) instead.
+# False: not one ``ptd_`` entry is called.
+DETERMINISTIC = False
+
+
+def _ws(floats: int, device) -> torch.Tensor:
+    """The workspace of one ``ptd_`` call: from torch's caching allocator on the CURRENT stream, so the main, the weight-gradient and
+    the spatial stream never share one; the caller holds it until its launches are enqueued, then the block goes back to that
+    stream's pool and only launches behind them on the same stream can get it again."""
+    return torch.empty(max(int(floats), 2), dtype=torch.float32, device=device)
 
 
 def _beside(fn: Callable[[], None], *tensors: torch.Tensor) -> None:
@@ -149,7 +160,12 @@ def gemm(A, B, Cm, M, N, K, sa, sb, sc, *, nb=(1, 1, 1), ba=(0, 0, 0), bb=(0, 0,
     p.alpha, p.out_mode, p.splits = float(alpha), out_mode, splits
     if gather is not None:
         (p.g_H, p.g_W, p.g_OH, p.g_OW, p.g_KH, p.g_KW, p.g_stride, p.g_pad_h, p.g_pad_w, p.g_ld) = gather
-    hip.checked().pt_gemm_f16(C.byref(p), _stream())
+    L = hip.checked()
+    if DETERMINISTIC and out_mode >= 2:                       # weight gradients: split-K through a workspace, no atomics
+        ws = _ws(L.ptd_gemm_ws_floats(C.byref(p)), tc.device)
+        L.ptd_gemm_f16(C.byref(p), ws.data_ptr(), ws.numel(), _stream())
+    else:
+        L.pt_gemm_f16(C.byref(p), _stream())
     if GEMM_LOG is not None:
         GEMM_LOG.append((M, N, K, nb[0] * nb[1] * nb[2], "T" if sa[0] == 1 else "N", "T" if sb[1] == 1 else "N", out_mode, splits, gather is not None))
 
@@ -173,7 +189,12 @@ def gemv(x: torch.Tensor, pw: Packed, res: Optional[torch.Tensor] = None) -> tor
 
 def colsum(dy: torch.Tensor, rows_per_seg: int, nseg: int, out: torch.Tensor, ncols: Optional[int] = None) -> None:
     """``out[seg, c] += sum_rows dy`` (fp32 ``out``)."""
-    hip.checked().pt_colsum_f16(dy.data_ptr(), rows_per_seg, nseg, ncols or dy.shape[-1], dy.stride(-2), out.data_ptr(), _stream())
+    L, Cc = hip.checked(), ncols or dy.shape[-1]
+    if DETERMINISTIC:
+        ws = _ws(L.ptd_colsum_ws_floats(rows_per_seg, nseg, Cc), dy.device)
+        L.ptd_colsum_f16(dy.data_ptr(), rows_per_seg, nseg, Cc, dy.stride(-2), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    else:
+        L.pt_colsum_f16(dy.data_ptr(), rows_per_seg, nseg, Cc, dy.stride(-2), out.data_ptr(), _stream())
 
 
 def _split_k(tiles: int, K: int) -> int:
@@ -215,6 +236,7 @@ class ParamStore:
         for k in self.names:
             self.value(k).copy_(sd[k].to(device=device, dtype=torch.float32))
         self.version, self.trainable = 0, True
+        self.deterministic = False                    # ControlNetTrainer(deterministic=True): the trainer sets autodiff.DETERMINISTIC from it
         self.on_grad_ready = None
         self.flat16 = torch.empty(n, dtype=torch.float16, device=device)      # fp16 mirror: norm weights / biases are read from it
         self._mirror_version = -1
@@ -469,7 +491,8 @@ class Dense:
 
     def accumulate(self, x: torch.Tensor, dy: torch.Tensor, geom) -> None:
         """dW += dY^T X (gathered per tap; one ``[Co, Ci]`` matrix per tap in the store's tap-major layout), db += column sums
-        of dY.  Split-K over the pixels with fp32 atomics when the tile count alone would not fill the chip, else plain +=."""
+        of dY.  Split-K over the pixels with fp32 atomics when the tile count alone would not fill the chip, else plain +=
+        (``DETERMINISTIC``: the same splits through a workspace, added in split order)."""
         if not self.P.trainable:
             return
         gw, (T, Co, Ci) = self._raw(self.P.grad)
@@ -599,9 +622,15 @@ def groupnorm(tape: Tape, x: Var, A: Affine, *, rows_per_sample: int, n_samples:
         dx1 = None if x1 is None else torch.empty((rows, C1), dtype=torch.float16, device=dy.device)
         stat = torch.empty(4 * n_samples * groups, dtype=torch.float32, device=dy.device)
         dg, db = A.grads()
-        hip.checked().pt_groupnorm_bwd(x.v.data_ptr(), _ptr(None if x1 is None else x1.v), C0, C1, groups, rows_per_sample, n_samples, float(eps),
-                                       gm.data_ptr(), bt.data_ptr(), 1 if silu else 0, dy.data_ptr(), dx0.data_ptr(), _ptr(dx1), _ptr(dg), _ptr(db),
-                                       stat.data_ptr(), _stream())
+        L = hip.checked()
+        p1 = _ptr(None if x1 is None else x1.v)
+        if DETERMINISTIC:
+            ws = _ws(L.ptd_groupnorm_bwd_ws_floats(C0 + C1, groups, rows_per_sample, n_samples, 0 if dg is None else 1), dy.device)
+            L.ptd_groupnorm_bwd(x.v.data_ptr(), p1, C0, C1, groups, rows_per_sample, n_samples, float(eps), gm.data_ptr(), bt.data_ptr(), 1 if silu else 0,
+                                dy.data_ptr(), dx0.data_ptr(), _ptr(dx1), _ptr(dg), _ptr(db), stat.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        else:
+            L.pt_groupnorm_bwd(x.v.data_ptr(), p1, C0, C1, groups, rows_per_sample, n_samples, float(eps), gm.data_ptr(), bt.data_ptr(), 1 if silu else 0,
+                               dy.data_ptr(), dx0.data_ptr(), _ptr(dx1), _ptr(dg), _ptr(db), stat.data_ptr(), _stream())
         A.P.grad_ready(A.w, A.b)
         _acc(x, dx0)
         if x1 is not None:
@@ -620,8 +649,13 @@ def layernorm(tape: Tape, x: Var, A: Affine, eps: float = 1e-5) -> Var:
         dx = torch.empty_like(x.v)
         dg, db = A.grads()
         rowstat = None if dg is None else torch.empty(2 * M, dtype=torch.float32, device=dy.device)
-        hip.checked().pt_layernorm_bwd(x.v.data_ptr(), M, Cc, gm.data_ptr(), float(eps), dy.data_ptr(), dx.data_ptr(), _ptr(dg), _ptr(db),
-                                       _ptr(rowstat), _stream())
+        L = hip.checked()
+        if DETERMINISTIC and dg is not None:                  # (without parameter gradients nothing crosses workgroups)
+            ws = _ws(L.ptd_layernorm_bwd_ws_floats(M, Cc), dy.device)
+            L.ptd_layernorm_bwd(x.v.data_ptr(), M, Cc, gm.data_ptr(), float(eps), dy.data_ptr(), dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(rowstat), ws.data_ptr(), ws.numel(),
+                                _stream())
+        else:
+            L.pt_layernorm_bwd(x.v.data_ptr(), M, Cc, gm.data_ptr(), float(eps), dy.data_ptr(), dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(rowstat), _stream())
         A.P.grad_ready(A.w, A.b)
         _acc(x, dx)
 
@@ -720,10 +754,15 @@ def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
     def bwd(dy):
         if M.P.trainable:                                       # d alpha / d mix = alpha (1 - alpha): on the host, or in the kernel
             gm = M.P.gradient(M.name).data_ptr()
-            if ap is None:
+            ws = _ws(L.ptd_dot_diff_ws_floats(dy.numel()), dy.device) if DETERMINISTIC else None
+            if ap is None and ws is None:
                 L.pt_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al), gm, _stream())
-            else:
+            elif ap is None:
+                L.ptd_dot_diff(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), al * (1.0 - al), gm, ws.data_ptr(), ws.numel(), _stream())
+            elif ws is None:
                 L.pt_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, gm, _stream())
+            else:
+                L.ptd_dot_diff_dev(dy.data_ptr(), a.v.data_ptr(), b.v.data_ptr(), dy.numel(), ap, gm, ws.data_ptr(), ws.numel(), _stream())
             M.P.grad_ready(M.name)
         _acc(a, scaled(dy, 0))
         _acc(b, scaled(dy, 1))

@@ -5,6 +5,8 @@
 // buffers with atomics (the caller zeroes them once per optimizer step, so gradient accumulation over micro-batches is free).
 #include "pt_common.h"
 #include "../../include/posetraj_optim.h"
+#include "../../include/posetraj_det.h"
+#include "pt_fold.h"
 
 namespace {
 
@@ -33,12 +35,15 @@ __device__ __forceinline__ void fold_strip(float (*red)[256 * 2], const float* s
 //   dx = rstd (g gamma - (s1 + xh s2) / n),  s1 = sum_group g gamma,  s2 = sum_group g gamma xh
 // stat[sample][group][4] = (sum x - P_g, sum (x - P_g)^2, s1, s2) in fp32, P_g the group's pivot (pt_gn_pivot: mean = P_g + S / n).
 // Three passes: MODE 0 (x statistics), MODE 1 (s1, s2 and the parameter gradients), apply.  grid (slabs, strips, samples).
-template <int MODE>
+// DET (ptd_groupnorm_bwd): no atomics - a block's group sums go to part_stat[slab * strips + strip][sample][group][2] (zero for the
+// groups its strip does not touch), its channel sums to part_par[sample * slabs + slab][dgamma | dbeta][Ct]; pt_fold.h adds them up.
+template <int MODE, bool DET>
 __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__ x0, const f16* __restrict__ x1, int C0, int C1, int groups,
                                                          int64_t rows_per_sample, int rows_per_slab, float eps,
                                                          const f16* __restrict__ gamma, const f16* __restrict__ beta, int silu,
                                                          const f16* __restrict__ dy, float* __restrict__ stat,
-                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                         float* __restrict__ part_stat, float* __restrict__ part_par) {
     __shared__ float red[TY][256 * 2];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int slab = blockIdx.x, strip = blockIdx.y, sample = blockIdx.z;
@@ -95,7 +100,14 @@ __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__
         if (MODE == 1 && cc < Ct) {
             const float gm = (float)gamma[cc];
             wa = gm * a; wb = gm * b;
-            if (dgamma) { atomicAdd(dgamma + cc, b); atomicAdd(dbeta + cc, a); }
+            if (dgamma) {
+                if constexpr (DET) {
+                    float* pp = part_par + ((int64_t)sample * gridDim.x + slab) * 2 * Ct;
+                    pp[cc] = b; pp[Ct + cc] = a;
+                } else {
+                    atomicAdd(dgamma + cc, b); atomicAdd(dbeta + cc, a);
+                }
+            }
         }
         chan[ch * 2] = cc < Ct ? wa : 0.f;
         chan[ch * 2 + 1] = cc < Ct ? wb : 0.f;
@@ -104,6 +116,21 @@ __global__ __launch_bounds__(256) void gnb_reduce_kernel(const f16* __restrict__
     const int c_lo = strip * 256, c_hi = (c_lo + 256 < Ct) ? c_lo + 256 : Ct;
     const int g_lo = c_lo / cg, g_hi = (c_hi - 1) / cg;
     const int ng = g_hi - g_lo + 1;
+    if constexpr (DET) {
+        float* ps = part_stat + (((int64_t)slab * gridDim.y + strip) * gridDim.z + sample) * 2 * groups;
+        for (int i = threadIdx.x; i < 2 * groups; i += 256) {
+            const int g = i >> 1, which = i & 1;
+            float acc = 0.f;
+            if (g >= g_lo && g <= g_hi) {
+                int a0 = g * cg, a1 = a0 + cg;
+                if (a0 < c_lo) a0 = c_lo;
+                if (a1 > c_hi) a1 = c_hi;
+                for (int ch = a0; ch < a1; ++ch) acc += chan[(ch - c_lo) * 2 + which];
+            }
+            ps[i] = acc;
+        }
+        return;
+    }
     for (int i = threadIdx.x; i < 2 * ng; i += 256) {
         const int g = g_lo + (i >> 1), which = i & 1;
         int a0 = g * cg, a1 = a0 + cg;
@@ -162,11 +189,14 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const f16* __restrict__ 
 // one wave per row; a block of 4 waves owns 64 rows.  A lane keeps the dgamma / dbeta contributions of ITS channels (chunk
 // lane, lane + 64, ...: C <= 1536) in registers over the wave's 16 rows, the four waves meet in LDS, one global atomic per
 // channel and block.
+// DET (ptd_layernorm_bwd): the four waves leave their sums in LDS slots of their own, [wave][2][C], added in wave order into
+// part[block][dgamma | dbeta][C] - no LDS atomics, no global ones.
 constexpr int LN_MAXCH = 3;                          // chunks of 8 channels per lane (C <= 1536)
+template <bool DET>
 __global__ __launch_bounds__(256) void lnb_kernel(const f16* __restrict__ x, int64_t M, int C, const f16* __restrict__ gamma, float eps,
                                                   const f16* __restrict__ dy, f16* __restrict__ dx, float* __restrict__ dgamma,
-                                                  float* __restrict__ dbeta, int rows_per_block) {
-    extern __shared__ float lds[];                 // [2][C] when dgamma
+                                                  float* __restrict__ dbeta, int rows_per_block, float* __restrict__ part) {
+    extern __shared__ float lds[];                 // [2][C] when dgamma (DET: [4][2][C])
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int CH = C >> 3;
     float pg[LN_MAXCH][8], pb[LN_MAXCH][8];
@@ -174,7 +204,7 @@ __global__ __launch_bounds__(256) void lnb_kernel(const f16* __restrict__ x, int
     for (int u = 0; u < LN_MAXCH; ++u)
 #pragma unroll
         for (int j = 0; j < 8; ++j) { pg[u][j] = 0.f; pb[u][j] = 0.f; }
-    if (dgamma) {
+    if (!DET && dgamma) {
         for (int i = threadIdx.x; i < 2 * C; i += 256) lds[i] = 0.f;
         __syncthreads();
     }
@@ -232,6 +262,20 @@ __global__ __launch_bounds__(256) void lnb_kernel(const f16* __restrict__ x, int
                 *(f16x8*)(dx + r * C + ch * 8) = o;
             }
         }
+    }
+    if (DET && dgamma) {
+        float* mine = lds + wave * 2 * C;
+#pragma unroll
+        for (int u = 0; u < LN_MAXCH; ++u) {
+            const int ch = lane + 64 * u;
+            if (ch < CH)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { mine[ch * 8 + j] = pg[u][j]; mine[C + ch * 8 + j] = pb[u][j]; }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * C; i += 256)
+            part[(int64_t)blockIdx.x * 2 * C + i] = ((lds[i] + lds[2 * C + i]) + lds[4 * C + i]) + lds[6 * C + i];
+        return;
     }
     if (dgamma) {
 #pragma unroll
@@ -322,6 +366,8 @@ __global__ __launch_bounds__(256) void lnb_narrow_kernel(const f16* __restrict__
 }
 
 // dgamma[c] += sum_rows dy xh, dbeta[c] += sum_rows dy with (mean, rstd) per row from the pass above; grid (slabs, strips)
+// DET: dgamma is the workspace, part[slab][dgamma | dbeta][C]
+template <bool DET>
 __global__ __launch_bounds__(256) void lnb_param_kernel(const f16* __restrict__ x, const f16* __restrict__ dy, const float* __restrict__ rowstat,
                                                         int64_t M, int rows_per_slab, int C, float* __restrict__ dgamma, float* __restrict__ dbeta) {
     __shared__ float red[TY][256 * 2];
@@ -343,7 +389,14 @@ __global__ __launch_bounds__(256) void lnb_param_kernel(const f16* __restrict__ 
     }
     fold_strip(red, s, q, [&](int ch, float a, float b) {
         const int cc = strip * 256 + ch;
-        if (cc < C) { atomicAdd(dbeta + cc, a); atomicAdd(dgamma + cc, b); }
+        if (cc < C) {
+            if constexpr (DET) {
+                float* pp = dgamma + (int64_t)slab * 2 * C;
+                pp[cc] = b; pp[C + cc] = a;
+            } else {
+                atomicAdd(dbeta + cc, a); atomicAdd(dgamma + cc, b);
+            }
+        }
     });
 }
 
@@ -351,15 +404,21 @@ inline int slab_rows(int64_t rows_per_sample, int64_t other_blocks);
 
 template <int LPR>
 void launch_lnb_narrow(const f16* x, int64_t M, int C, const f16* gamma, float eps, const f16* dy, f16* dx, float* dgamma, float* dbeta,
-                       float* rowstat, hipStream_t s) {
+                       float* rowstat, hipStream_t s, float* ws = nullptr) {
     const int rpb = 64;
     const unsigned blocks = (unsigned)((M + rpb - 1) / rpb);
     if (dgamma) {
         hipLaunchKernelGGL((lnb_narrow_kernel<LPR, true>), dim3(blocks), dim3(256), 0, s, x, M, C, gamma, eps, dy, dx, rowstat, rpb);
         const int strips = (C + 255) / 256;
         const int rps = slab_rows(M, strips);
-        hipLaunchKernelGGL(lnb_param_kernel, dim3((unsigned)((M + rps - 1) / rps), strips), dim3(256), 0, s, x, dy, (const float*)rowstat, M, rps, C, dgamma,
-                           dbeta);
+        const int slabs = (int)((M + rps - 1) / rps);
+        if (ws) {
+            hipLaunchKernelGGL(lnb_param_kernel<true>, dim3(slabs, strips), dim3(256), 0, s, x, dy, (const float*)rowstat, M, rps, C, ws, (float*)nullptr);
+            FoldJob j = fold_job(ws, 2 * (int64_t)C, slabs, dgamma, 1);
+            j.n0 = C; j.grp = C; j.out1 = dbeta;
+            launch_fold<float>(s, j);
+        } else
+            hipLaunchKernelGGL(lnb_param_kernel<false>, dim3(slabs, strips), dim3(256), 0, s, x, dy, (const float*)rowstat, M, rps, C, dgamma, dbeta);
     } else {
         hipLaunchKernelGGL((lnb_narrow_kernel<LPR, false>), dim3(blocks), dim3(256), 0, s, x, M, C, gamma, eps, dy, dx, rowstat, rpb);
     }
@@ -368,6 +427,8 @@ void launch_lnb_narrow(const f16* x, int64_t M, int C, const f16* gamma, float e
 // ------------------------------------------------------------------------------------------ segmented column sums
 // out[seg, c] += sum over the rows of segment seg of dy[row, c]: bias gradients (one segment), the gradient of a per-frame /
 // per-clip row vector broadcast over its rows (time-embedding rows, collapsed cross-attention, frame position embedding).
+// DET: out is the workspace, part[slab][seg][C]
+template <bool DET>
 __global__ __launch_bounds__(256) void colsum_kernel(const f16* __restrict__ dy, int64_t rows_per_seg, int rows_per_slab, int C, int ld,
                                                      float* __restrict__ out) {
     __shared__ float red[TY][256 * 2];
@@ -406,7 +467,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const f16* __restrict__ dy,
     }
     fold_strip(red, s, q, [&](int ch, float a, float) {
         const int cc = strip * 256 + ch;
-        if (cc < C) atomicAdd(out + (int64_t)seg * C + cc, a);
+        if (cc < C) {
+            if constexpr (DET) out[((int64_t)slab * gridDim.z + seg) * C + cc] = a;
+            else atomicAdd(out + (int64_t)seg * C + cc, a);
+        }
     });
 }
 
@@ -496,7 +560,8 @@ __global__ __launch_bounds__(256) void lerp_kernel(const f16* __restrict__ a, co
     }
 }
 
-// out += scale * sum_i dy_i (a_i - b_i)     (gradient of the blend weight; fp32, one atomic per block)
+// out += scale * sum_i dy_i (a_i - b_i)     (gradient of the blend weight; fp32, one atomic per block; DET: out[block] = its term)
+template <bool DET>
 __global__ __launch_bounds__(256) void dot_diff_kernel(const f16* __restrict__ dy, const f16* __restrict__ a, const f16* __restrict__ b,
                                                        int64_t n, float scale, float* __restrict__ out) {
     __shared__ float red[4];
@@ -506,7 +571,11 @@ __global__ __launch_bounds__(256) void dot_diff_kernel(const f16* __restrict__ d
     acc = pt_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, scale * (red[0] + red[1] + red[2] + red[3]));
+    if (threadIdx.x == 0) {
+        const float v = scale * (red[0] + red[1] + red[2] + red[3]);
+        if constexpr (DET) out[blockIdx.x] = v;
+        else atomicAdd(out, v);
+    }
 }
 
 // The same three with the blend weight read from DEVICE memory (round 6: the training step as a hipGraph - a captured launch cannot take a
@@ -523,6 +592,7 @@ __global__ __launch_bounds__(256) void lerp_dev_kernel(const f16* __restrict__ a
     }
 }
 
+template <bool DET>
 __global__ __launch_bounds__(256) void dot_diff_dev_kernel(const f16* __restrict__ dy, const f16* __restrict__ a, const f16* __restrict__ b,
                                                            int64_t n, const float* __restrict__ alpha_p, float* __restrict__ out) {
     __shared__ float red[4];
@@ -533,7 +603,11 @@ __global__ __launch_bounds__(256) void dot_diff_dev_kernel(const f16* __restrict
     acc = pt_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, scale * (red[0] + red[1] + red[2] + red[3]));
+    if (threadIdx.x == 0) {
+        const float v = scale * (red[0] + red[1] + red[2] + red[3]);
+        if constexpr (DET) out[blockIdx.x] = v;
+        else atomicAdd(out, v);
+    }
 }
 
 // y = k x (one_minus = 0) or (1 - k) x (one_minus = 1), k from device memory
@@ -890,6 +964,8 @@ __global__ __launch_bounds__(256) void adam8_dequant_kernel(const uint8_t* __res
 }
 
 // out[0] += sum g^2 (fp32 in, fp64 block sums); a non-finite gradient anywhere makes the result non-finite (the GradScaler check)
+// DET: out[block] = the block's sum
+template <bool DET>
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ out) {
     __shared__ double red[256];
     double acc = 0.0;
@@ -900,7 +976,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
         if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) atomicAdd(out, red[0]);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) out[blockIdx.x] = red[0];
+        else atomicAdd(out, red[0]);
+    }
 }
 
 
@@ -995,66 +1074,190 @@ inline int slab_rows(int64_t rows_per_sample, int64_t other_blocks) {
 
 }  // namespace
 
+// The host side of a reduction and of its deterministic twin (include/posetraj_det.h) is ONE function: `det` only chooses the
+// kernels' DET instance, checks the workspace and adds the fold launch.  With det == false nothing differs from what it was.
+struct GnGeom { int strips, rps, slabs; int64_t stat_floats, par_floats; };
+static GnGeom gn_geom(int Ct, int groups, int64_t rows_per_sample, int n_samples, bool with_params) {
+    GnGeom g;
+    g.strips = (Ct + 255) / 256;
+    g.rps = slab_rows(rows_per_sample, (int64_t)g.strips * n_samples);
+    g.slabs = (int)((rows_per_sample + g.rps - 1) / g.rps);
+    g.stat_floats = (int64_t)g.slabs * g.strips * n_samples * groups * 2;
+    g.par_floats = with_params ? (int64_t)n_samples * g.slabs * 2 * Ct : 0;
+    return g;
+}
+
+static int groupnorm_bwd_launch(const char* who, bool det, const void* x0, const void* x1, int32_t C0, int32_t C1, int32_t groups,
+                                int64_t rows_per_sample, int32_t n_samples, float eps, const void* gamma, const void* beta, int32_t silu,
+                                const void* dy, void* dx0, void* dx1, float* dgamma, float* dbeta, float* stat, float* ws, int64_t ws_floats,
+                                void* stream) {
+    const int Ct = C0 + C1;
+    PT_CHECK(x0 && gamma && beta && dy && dx0 && stat, "%s: null pointer", who);
+    PT_CHECK((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)dy | (uintptr_t)dx0 | (uintptr_t)dx1) & 15) == 0, "%s: 16-byte aligned rows required", who);
+    PT_CHECK(C0 > 0 && C0 % 8 == 0 && C1 >= 0 && C1 % 8 == 0 && (C1 == 0 || (x1 && dx1)), "%s: channel counts %d + %d", who, C0, C1);
+    PT_CHECK(groups > 0 && Ct % groups == 0, "%s: %d channels / %d groups", who, Ct, groups);
+    PT_CHECK(rows_per_sample > 0 && n_samples > 0 && n_samples < 65536, "%s: bad sizes", who);
+    PT_CHECK((dgamma == nullptr) == (dbeta == nullptr), "%s: dgamma and dbeta come together", who);
+    hipStream_t s = (hipStream_t)stream;
+    const GnGeom g = gn_geom(Ct, groups, rows_per_sample, n_samples, dgamma != nullptr);
+    const dim3 grid(g.slabs, g.strips, n_samples);
+#define PT_GNB_ARGS (const f16*)x0, (const f16*)x1, C0, C1, groups, rows_per_sample, g.rps, eps, (const f16*)gamma, (const f16*)beta, silu, (const f16*)dy
+    if (det) {
+        PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= g.stat_floats + g.par_floats, "%s: the workspace holds %lld floats, %lld needed", who,
+                 (long long)(ws ? ws_floats : 0), (long long)(g.stat_floats + g.par_floats));
+        float* ps = ws;
+        float* pp = ws + g.stat_floats;
+        const int64_t ns = (int64_t)n_samples * groups * 2;
+        FoldJob js = fold_job(ps, ns, g.slabs * g.strips, stat, 0);
+        js.grp = 2; js.stride = 4;
+        hipLaunchKernelGGL((gnb_reduce_kernel<0, true>), grid, dim3(256), 0, s, PT_GNB_ARGS, stat, dgamma, dbeta, ps, pp);
+        launch_fold<float>(s, js);
+        hipLaunchKernelGGL((gnb_reduce_kernel<1, true>), grid, dim3(256), 0, s, PT_GNB_ARGS, stat, dgamma, dbeta, ps, pp);
+        js.off = 2;
+        if (dgamma) {
+            FoldJob jp = fold_job(pp, 2 * (int64_t)Ct, n_samples * g.slabs, dgamma, 1);
+            jp.n0 = Ct; jp.grp = Ct; jp.out1 = dbeta;
+            launch_fold<float>(s, js, &jp);
+        } else {
+            launch_fold<float>(s, js);
+        }
+    } else {
+        if (hipMemsetAsync(stat, 0, sizeof(float) * 4 * (size_t)n_samples * groups, s) != hipSuccess) { pt_set_error("%s: memset failed", who); return 2; }
+        hipLaunchKernelGGL((gnb_reduce_kernel<0, false>), grid, dim3(256), 0, s, PT_GNB_ARGS, stat, dgamma, dbeta, (float*)nullptr, (float*)nullptr);
+        hipLaunchKernelGGL((gnb_reduce_kernel<1, false>), grid, dim3(256), 0, s, PT_GNB_ARGS, stat, dgamma, dbeta, (float*)nullptr, (float*)nullptr);
+    }
+    hipLaunchKernelGGL(gnb_apply_kernel, grid, dim3(256), 0, s, PT_GNB_ARGS, (const float*)stat, (f16*)dx0, (f16*)dx1);
+#undef PT_GNB_ARGS
+    PT_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int pt_groupnorm_bwd(const void* x0, const void* x1, int32_t C0, int32_t C1, int32_t groups, int64_t rows_per_sample,
                                 int32_t n_samples, float eps, const void* gamma, const void* beta, int32_t silu, const void* dy,
                                 void* dx0, void* dx1, float* dgamma, float* dbeta, float* stat, void* stream) {
-    const int Ct = C0 + C1;
-    PT_CHECK(x0 && gamma && beta && dy && dx0 && stat, "pt_groupnorm_bwd: null pointer");
-    PT_CHECK((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)dy | (uintptr_t)dx0 | (uintptr_t)dx1) & 15) == 0, "pt_groupnorm_bwd: 16-byte aligned rows required");
-    PT_CHECK(C0 > 0 && C0 % 8 == 0 && C1 >= 0 && C1 % 8 == 0 && (C1 == 0 || (x1 && dx1)), "pt_groupnorm_bwd: channel counts %d + %d", C0, C1);
-    PT_CHECK(groups > 0 && Ct % groups == 0, "pt_groupnorm_bwd: %d channels / %d groups", Ct, groups);
-    PT_CHECK(rows_per_sample > 0 && n_samples > 0 && n_samples < 65536, "pt_groupnorm_bwd: bad sizes");
-    PT_CHECK((dgamma == nullptr) == (dbeta == nullptr), "pt_groupnorm_bwd: dgamma and dbeta come together");
+    return groupnorm_bwd_launch("pt_groupnorm_bwd", false, x0, x1, C0, C1, groups, rows_per_sample, n_samples, eps, gamma, beta, silu, dy, dx0, dx1,
+                                dgamma, dbeta, stat, nullptr, 0, stream);
+}
+
+extern "C" int64_t ptd_groupnorm_bwd_ws_floats(int32_t channels, int32_t groups, int64_t rows_per_sample, int32_t n_samples, int32_t with_params) {
+    if (channels <= 0 || groups <= 0 || rows_per_sample <= 0 || n_samples <= 0) return 0;
+    const GnGeom g = gn_geom(channels, groups, rows_per_sample, n_samples, with_params != 0);
+    return g.stat_floats + g.par_floats;
+}
+
+extern "C" int ptd_groupnorm_bwd(const void* x0, const void* x1, int32_t C0, int32_t C1, int32_t groups, int64_t rows_per_sample,
+                                 int32_t n_samples, float eps, const void* gamma, const void* beta, int32_t silu, const void* dy,
+                                 void* dx0, void* dx1, float* dgamma, float* dbeta, float* stat, float* ws, int64_t ws_floats, void* stream) {
+    return groupnorm_bwd_launch("ptd_groupnorm_bwd", true, x0, x1, C0, C1, groups, rows_per_sample, n_samples, eps, gamma, beta, silu, dy, dx0, dx1,
+                                dgamma, dbeta, stat, ws, ws_floats, stream);
+}
+
+// blocks of the wide LayerNorm backward (one wave per row) and rows per block
+static int64_t lnb_wide_blocks(int64_t M, int* rows_per_block) {
+    // the wide rows of this network are its low-resolution levels (630 / 2 520 rows of 1 280 channels): 64 rows per
+    // block left 10 - 40 blocks for 256 CUs (83 us per launch); 8 ... 64 rows per block, aiming at ~512 blocks
+    int rpb = (int)((M + 511) / 512);
+    rpb = rpb < 8 ? 8 : (rpb > 64 ? 64 : (rpb + 3) / 4 * 4);
+    *rows_per_block = rpb;
+    return (M + rpb - 1) / rpb;
+}
+
+// partials of the parameter gradients: slabs of lnb_param_kernel (narrow rows) or blocks of lnb_kernel
+static int64_t lnb_partials(int64_t M, int Cc) {
+    if (Cc / 8 <= 96) {
+        const int rps = slab_rows(M, (Cc + 255) / 256);
+        return (M + rps - 1) / rps;
+    }
+    int rpb;
+    return lnb_wide_blocks(M, &rpb);
+}
+
+static int layernorm_bwd_launch(const char* who, bool det, const void* x, int64_t M, int32_t Cc, const void* gamma, float eps, const void* dy,
+                                void* dx, float* dgamma, float* dbeta, float* rowstat, float* ws, int64_t ws_floats, void* stream) {
+    PT_CHECK(x && gamma && dy && dx, "%s: null pointer", who);
+    PT_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma) & 15) == 0, "%s: 16-byte aligned rows required", who);
+    PT_CHECK(M > 0 && Cc > 0 && Cc % 8 == 0 && Cc <= 512 * LN_MAXCH, "%s: bad sizes (M %lld, C %d)", who, (long long)M, Cc);
+    PT_CHECK((dgamma == nullptr) == (dbeta == nullptr), "%s: dgamma and dbeta come together", who);
+    PT_CHECK(!dgamma || rowstat, "%s: parameter gradients need the 2 M floats of rowstat scratch", who);
+    det = det && dgamma;                                           // without parameter gradients nothing is reduced across blocks
+    if (det) {
+        const int64_t need = lnb_partials(M, Cc) * 2 * Cc;
+        PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= need, "%s: the workspace holds %lld floats, %lld needed", who,
+                 (long long)(ws ? ws_floats : 0), (long long)need);
+    }
+    float* w = det ? ws : nullptr;
+    const int CH = Cc / 8;
     hipStream_t s = (hipStream_t)stream;
-    const int strips = (Ct + 255) / 256;
-    const int rps = slab_rows(rows_per_sample, (int64_t)strips * n_samples);
-    const int slabs = (int)((rows_per_sample + rps - 1) / rps);
-    if (hipMemsetAsync(stat, 0, sizeof(float) * 4 * (size_t)n_samples * groups, s) != hipSuccess) { pt_set_error("pt_groupnorm_bwd: memset failed"); return 2; }
-    const dim3 grid(slabs, strips, n_samples);
-    hipLaunchKernelGGL(gnb_reduce_kernel<0>, grid, dim3(256), 0, s, (const f16*)x0, (const f16*)x1, C0, C1, groups, rows_per_sample, rps, eps,
-                       (const f16*)gamma, (const f16*)beta, silu, (const f16*)dy, stat, dgamma, dbeta);
-    hipLaunchKernelGGL(gnb_reduce_kernel<1>, grid, dim3(256), 0, s, (const f16*)x0, (const f16*)x1, C0, C1, groups, rows_per_sample, rps, eps,
-                       (const f16*)gamma, (const f16*)beta, silu, (const f16*)dy, stat, dgamma, dbeta);
-    hipLaunchKernelGGL(gnb_apply_kernel, grid, dim3(256), 0, s, (const f16*)x0, (const f16*)x1, C0, C1, groups, rows_per_sample, rps, eps,
-                       (const f16*)gamma, (const f16*)beta, silu, (const f16*)dy, (const float*)stat, (f16*)dx0, (f16*)dx1);
-    PT_LAUNCH_CHECK("pt_groupnorm_bwd");
+    if (CH <= 24) launch_lnb_narrow<8>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s, w);
+    else if (CH <= 48) launch_lnb_narrow<16>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s, w);
+    else if (CH <= 96) launch_lnb_narrow<32>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s, w);
+    else {
+        int rpb;
+        const int64_t blocks = lnb_wide_blocks(M, &rpb);
+        if (det) {
+            hipLaunchKernelGGL(lnb_kernel<true>, dim3((unsigned)blocks), dim3(256), sizeof(float) * 8 * Cc, s, (const f16*)x, M, Cc, (const f16*)gamma, eps,
+                               (const f16*)dy, (f16*)dx, dgamma, dbeta, rpb, w);
+            FoldJob j = fold_job(w, 2 * (int64_t)Cc, (int)blocks, dgamma, 1);
+            j.n0 = Cc; j.grp = Cc; j.out1 = dbeta;
+            launch_fold<float>(s, j);
+        } else {
+            hipLaunchKernelGGL(lnb_kernel<false>, dim3((unsigned)blocks), dim3(256), dgamma ? sizeof(float) * 2 * Cc : 0, s, (const f16*)x, M, Cc,
+                               (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rpb, (float*)nullptr);
+        }
+    }
+    PT_LAUNCH_CHECK(who);
     return 0;
 }
 
 extern "C" int pt_layernorm_bwd(const void* x, int64_t M, int32_t Cc, const void* gamma, float eps, const void* dy, void* dx,
                                 float* dgamma, float* dbeta, float* rowstat, void* stream) {
-    PT_CHECK(x && gamma && dy && dx, "pt_layernorm_bwd: null pointer");
-    PT_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma) & 15) == 0, "pt_layernorm_bwd: 16-byte aligned rows required");
-    PT_CHECK(M > 0 && Cc > 0 && Cc % 8 == 0 && Cc <= 512 * LN_MAXCH, "pt_layernorm_bwd: bad sizes (M %lld, C %d)", (long long)M, Cc);
-    PT_CHECK((dgamma == nullptr) == (dbeta == nullptr), "pt_layernorm_bwd: dgamma and dbeta come together");
-    PT_CHECK(!dgamma || rowstat, "pt_layernorm_bwd: parameter gradients need the 2 M floats of rowstat scratch");
-    const int CH = Cc / 8;
+    return layernorm_bwd_launch("pt_layernorm_bwd", false, x, M, Cc, gamma, eps, dy, dx, dgamma, dbeta, rowstat, nullptr, 0, stream);
+}
+
+extern "C" int64_t ptd_layernorm_bwd_ws_floats(int64_t M, int32_t Cc) {
+    return (M > 0 && Cc > 0) ? lnb_partials(M, Cc) * 2 * Cc : 0;
+}
+
+extern "C" int ptd_layernorm_bwd(const void* x, int64_t M, int32_t Cc, const void* gamma, float eps, const void* dy, void* dx,
+                                 float* dgamma, float* dbeta, float* rowstat, float* ws, int64_t ws_floats, void* stream) {
+    return layernorm_bwd_launch("ptd_layernorm_bwd", true, x, M, Cc, gamma, eps, dy, dx, dgamma, dbeta, rowstat, ws, ws_floats, stream);
+}
+
+static int colsum_launch(const char* who, bool det, const void* dy, int64_t rows_per_seg, int32_t nseg, int32_t Cc, int32_t ld, float* out,
+                         float* ws, int64_t ws_floats, void* stream) {
+    PT_CHECK(dy && out, "%s: null pointer", who);
+    PT_CHECK(rows_per_seg > 0 && nseg > 0 && nseg < 65536 && Cc > 0 && ld >= Cc && ld % 8 == 0, "%s: bad sizes", who);
+    const int strips = (Cc + 255) / 256;
+    const int rps = slab_rows(rows_per_seg, (int64_t)strips * nseg);
+    const int slabs = (int)((rows_per_seg + rps - 1) / rps);
+    const dim3 grid(slabs, strips, nseg);
     hipStream_t s = (hipStream_t)stream;
-    if (CH <= 24) launch_lnb_narrow<8>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s);
-    else if (CH <= 48) launch_lnb_narrow<16>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s);
-    else if (CH <= 96) launch_lnb_narrow<32>((const f16*)x, M, Cc, (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rowstat, s);
-    else {
-        // the wide rows of this network are its low-resolution levels (630 / 2 520 rows of 1 280 channels): 64 rows per
-        // block left 10 - 40 blocks for 256 CUs (83 us per launch); 8 ... 64 rows per block, aiming at ~512 blocks
-        int rpb = (int)((M + 511) / 512);
-        rpb = rpb < 8 ? 8 : (rpb > 64 ? 64 : (rpb + 3) / 4 * 4);
-        const int64_t blocks = (M + rpb - 1) / rpb;
-        hipLaunchKernelGGL(lnb_kernel, dim3((unsigned)blocks), dim3(256), dgamma ? sizeof(float) * 2 * Cc : 0, s, (const f16*)x, M, Cc,
-                           (const f16*)gamma, eps, (const f16*)dy, (f16*)dx, dgamma, dbeta, rpb);
+    if (det) {
+        const int64_t n = (int64_t)nseg * Cc;
+        PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= slabs * n, "%s: the workspace holds %lld floats, %lld needed", who,
+                 (long long)(ws ? ws_floats : 0), (long long)(slabs * n));
+        hipLaunchKernelGGL(colsum_kernel<true>, grid, dim3(256), 0, s, (const f16*)dy, rows_per_seg, rps, Cc, ld, ws);
+        launch_fold<float>(s, fold_job(ws, n, slabs, out, 1));
+    } else {
+        hipLaunchKernelGGL(colsum_kernel<false>, grid, dim3(256), 0, s, (const f16*)dy, rows_per_seg, rps, Cc, ld, out);
     }
-    PT_LAUNCH_CHECK("pt_layernorm_bwd");
+    PT_LAUNCH_CHECK(who);
     return 0;
 }
 
 extern "C" int pt_colsum_f16(const void* dy, int64_t rows_per_seg, int32_t nseg, int32_t Cc, int32_t ld, float* out, void* stream) {
-    PT_CHECK(dy && out, "pt_colsum_f16: null pointer");
-    PT_CHECK(rows_per_seg > 0 && nseg > 0 && nseg < 65536 && Cc > 0 && ld >= Cc && ld % 8 == 0, "pt_colsum_f16: bad sizes");
-    const int strips = (Cc + 255) / 256;
-    const int rps = slab_rows(rows_per_seg, (int64_t)strips * nseg);
-    const int slabs = (int)((rows_per_seg + rps - 1) / rps);
-    hipLaunchKernelGGL(colsum_kernel, dim3(slabs, strips, nseg), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, rows_per_seg, rps, Cc, ld, out);
-    PT_LAUNCH_CHECK("pt_colsum_f16");
-    return 0;
+    return colsum_launch("pt_colsum_f16", false, dy, rows_per_seg, nseg, Cc, ld, out, nullptr, 0, stream);
+}
+
+extern "C" int64_t ptd_colsum_ws_floats(int64_t rows_per_seg, int32_t nseg, int32_t Cc) {
+    if (rows_per_seg <= 0 || nseg <= 0 || Cc <= 0) return 0;
+    const int rps = slab_rows(rows_per_seg, (int64_t)((Cc + 255) / 256) * nseg);
+    return (rows_per_seg + rps - 1) / rps * nseg * Cc;
+}
+
+extern "C" int ptd_colsum_f16(const void* dy, int64_t rows_per_seg, int32_t nseg, int32_t Cc, int32_t ld, float* out, float* ws,
+                              int64_t ws_floats, void* stream) {
+    return colsum_launch("ptd_colsum_f16", true, dy, rows_per_seg, nseg, Cc, ld, out, ws, ws_floats, stream);
 }
 
 extern "C" int pt_softmax_rows(const float* S, int64_t rows, int32_t n, int64_t ld, void* P, int64_t ldp, void* stream) {
@@ -1101,13 +1304,48 @@ extern "C" int pt_lerp_f16(const void* a, const void* b, float alpha, int64_t n,
     return 0;
 }
 
+static unsigned dot_diff_blocks(int64_t n) {
+    const unsigned blocks = ew_blocks(n);
+    return blocks > 1024 ? 1024 : blocks;
+}
+
+// alpha_dev == nullptr: the host's `scale`; else scale = alpha (1 - alpha) from device memory
+static int dot_diff_launch(const char* who, bool det, const void* dy, const void* a, const void* b, int64_t n, float scale, const float* alpha_dev,
+                           float* out, float* ws, int64_t ws_floats, void* stream) {
+    const unsigned blocks = dot_diff_blocks(n > 0 ? n : 1);
+    hipStream_t s = (hipStream_t)stream;
+    if (det) {
+        PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= (int64_t)blocks, "%s: the workspace holds %lld floats, %lld needed", who,
+                 (long long)(ws ? ws_floats : 0), (long long)blocks);
+        if (alpha_dev) hipLaunchKernelGGL(dot_diff_dev_kernel<true>, dim3(blocks), dim3(256), 0, s, (const f16*)dy, (const f16*)a, (const f16*)b, n, alpha_dev, ws);
+        else hipLaunchKernelGGL(dot_diff_kernel<true>, dim3(blocks), dim3(256), 0, s, (const f16*)dy, (const f16*)a, (const f16*)b, n, scale, ws);
+        launch_fold<float>(s, fold_job(ws, 1, (int)blocks, out, 1));
+    } else if (alpha_dev) {
+        hipLaunchKernelGGL(dot_diff_dev_kernel<false>, dim3(blocks), dim3(256), 0, s, (const f16*)dy, (const f16*)a, (const f16*)b, n, alpha_dev, out);
+    } else {
+        hipLaunchKernelGGL(dot_diff_kernel<false>, dim3(blocks), dim3(256), 0, s, (const f16*)dy, (const f16*)a, (const f16*)b, n, scale, out);
+    }
+    PT_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int pt_dot_diff(const void* dy, const void* a, const void* b, int64_t n, float scale, float* out, void* stream) {
     PT_CHECK(dy && a && out && n > 0, "pt_dot_diff: bad arguments");
-    unsigned blocks = ew_blocks(n);
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(dot_diff_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, (const f16*)a, (const f16*)b, n, scale, out);
-    PT_LAUNCH_CHECK("pt_dot_diff");
-    return 0;
+    return dot_diff_launch("pt_dot_diff", false, dy, a, b, n, scale, nullptr, out, nullptr, 0, stream);
+}
+
+extern "C" int64_t ptd_dot_diff_ws_floats(int64_t n) { return n > 0 ? (int64_t)dot_diff_blocks(n) : 0; }
+
+extern "C" int ptd_dot_diff(const void* dy, const void* a, const void* b, int64_t n, float scale, float* out, float* ws, int64_t ws_floats,
+                            void* stream) {
+    PT_CHECK(dy && a && out && n > 0, "ptd_dot_diff: bad arguments");
+    return dot_diff_launch("ptd_dot_diff", true, dy, a, b, n, scale, nullptr, out, ws, ws_floats, stream);
+}
+
+extern "C" int ptd_dot_diff_dev(const void* dy, const void* a, const void* b, int64_t n, const float* alpha_dev, float* out, float* ws,
+                                int64_t ws_floats, void* stream) {
+    PT_CHECK(dy && a && out && alpha_dev && n > 0, "ptd_dot_diff_dev: bad arguments");
+    return dot_diff_launch("ptd_dot_diff_dev", true, dy, a, b, n, 0.f, alpha_dev, out, ws, ws_floats, stream);
 }
 
 extern "C" int pt_lerp_f16_dev(const void* a, const void* b, const float* alpha_dev, int64_t n, void* out, void* stream) {
@@ -1119,11 +1357,7 @@ extern "C" int pt_lerp_f16_dev(const void* a, const void* b, const float* alpha_
 
 extern "C" int pt_dot_diff_dev(const void* dy, const void* a, const void* b, int64_t n, const float* alpha_dev, float* out, void* stream) {
     PT_CHECK(dy && a && out && alpha_dev && n > 0, "pt_dot_diff_dev: bad arguments");
-    unsigned blocks = ew_blocks(n);
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(dot_diff_dev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)dy, (const f16*)a, (const f16*)b, n, alpha_dev, out);
-    PT_LAUNCH_CHECK("pt_dot_diff_dev");
-    return 0;
+    return dot_diff_launch("pt_dot_diff_dev", false, dy, a, b, n, 0.f, alpha_dev, out, nullptr, 0, stream);
 }
 
 extern "C" int pt_scale_f16_dev(const void* x, const float* k_dev, int32_t one_minus, int64_t n, void* y, void* stream) {
@@ -1291,12 +1525,31 @@ extern "C" int pto_adam8_dequant_f32(const void* state1, const void* state2, con
     return 0;
 }
 
+static unsigned sumsq_blocks(int64_t n) {
+    const unsigned blocks = ew_blocks(n);
+    return blocks > 2048 ? 2048 : blocks;
+}
+
 extern "C" int pt_sumsq_f32(const float* g, int64_t n, double* out, void* stream) {
     PT_CHECK(g && out && n > 0, "pt_sumsq_f32: bad arguments");
-    unsigned blocks = ew_blocks(n);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, out);
+    hipLaunchKernelGGL(sumsq_kernel<false>, dim3(sumsq_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, out);
     PT_LAUNCH_CHECK("pt_sumsq_f32");
+    return 0;
+}
+
+extern "C" int ptd_abi_version(void) { return PT_DET_ABI_VERSION; }
+
+extern "C" int64_t ptd_sumsq_ws_floats(int64_t n) { return n > 0 ? 2 * (int64_t)sumsq_blocks(n) : 0; }
+
+extern "C" int ptd_sumsq_f32(const float* g, int64_t n, double* out, float* ws, int64_t ws_floats, void* stream) {
+    PT_CHECK(g && out && n > 0, "ptd_sumsq_f32: bad arguments");
+    const unsigned blocks = sumsq_blocks(n);
+    PT_CHECK(ws && ((uintptr_t)ws & 7) == 0 && ws_floats >= 2 * (int64_t)blocks, "ptd_sumsq_f32: the workspace (8-byte aligned) holds %lld floats, %lld needed",
+             (long long)(ws ? ws_floats : 0), (long long)(2 * (int64_t)blocks));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sumsq_kernel<true>, dim3(blocks), dim3(256), 0, s, g, n, (double*)ws);
+    launch_fold<double>(s, fold_job(ws, 1, (int)blocks, out, 1));
+    PT_LAUNCH_CHECK("ptd_sumsq_f32");
     return 0;
 }
 

@@ -16,6 +16,8 @@
 // the [row][k] operand reads the same two quads (two 8-byte reads), so both fragments agree on the k order.
 // Four tile shapes (waves 2 x 2, TM x TN MFMA tiles per wave), a one-dimensional XCD-aware grid (see the kernel).
 #include "pt_common.h"
+#include "../../include/posetraj_det.h"
+#include "pt_fold.h"
 
 namespace {
 
@@ -162,6 +164,7 @@ struct GemmK {
     float alpha;
     int out_mode;            // 0 fp16 store, 1 fp32 store, 2 fp32 atomic add, 3 fp32 += (single writer)
     int gKW;
+    int64_t split_stride;    // elements between the C images of two splits: 0, or the slice of ptd_gemm_f16's workspace
 };
 
 template <int TM, int TN, bool FAST>
@@ -195,7 +198,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmK p) {
     A.p += b0 * p.ba[0] + b1 * p.ba[1] + b2 * p.ba[2];
     B.p += b0 * p.bb[0] + b1 * p.bb[1] + b2 * p.bb[2];
     if (g.on) { g.ky = b2 / p.gKW; g.kx = b2 % p.gKW; }
-    const int64_t coff = b0 * p.bc[0] + b1 * p.bc[1] + b2 * p.bc[2];
+    const int64_t coff = b0 * p.bc[0] + b1 * p.bc[1] + b2 * p.bc[2] + split * p.split_stride;
     const bool akc = A.s_k == 1, bkc = B.s_k == 1 && !g.on;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int64_t k_begin = (int64_t)split * p.k_per_split;
@@ -309,40 +312,72 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmK p) {
 
 }  // namespace
 
-extern "C" int pt_gemm_f16(const pt_gemm_params* q, void* stream) {
-    PT_CHECK(q->A && q->B && q->C, "pt_gemm_f16: null operand");
-    PT_CHECK(q->M > 0 && q->N > 0 && q->K >= 0, "pt_gemm_f16: empty problem (M %d N %d K %lld)", q->M, q->N, (long long)q->K);
-    PT_CHECK(q->sa_m == 1 || q->sa_k == 1, "pt_gemm_f16: A needs a unit stride along m or k (%lld, %lld)", (long long)q->sa_m, (long long)q->sa_k);
-    PT_CHECK(q->sb_n == 1 || q->sb_k == 1, "pt_gemm_f16: B needs a unit stride along n or k (%lld, %lld)", (long long)q->sb_n, (long long)q->sb_k);
-    PT_CHECK(q->out_mode >= 0 && q->out_mode <= 3, "pt_gemm_f16: out_mode %d", q->out_mode);
-    PT_CHECK(q->nb0 >= 1 && q->nb1 >= 1 && q->nb2 >= 1, "pt_gemm_f16: batch counts must be >= 1");
-    const int gather = q->g_H > 0;
-    if (gather) {
-        PT_CHECK(q->K < (1LL << 32), "pt_gemm_f16: gather: more than 2^32 output pixels");
-        PT_CHECK(q->sb_n == 1, "pt_gemm_f16: the gathered operand is channels-last (unit stride along n)");
-        PT_CHECK(q->g_KH >= 1 && q->g_KW >= 1 && q->nb2 == q->g_KH * q->g_KW, "pt_gemm_f16: gather: the innermost batch runs over the %d x %d taps", q->g_KH, q->g_KW);
-        PT_CHECK(q->g_stride >= 1 && q->g_OH >= 1 && q->g_OW >= 1 && q->g_W >= 1, "pt_gemm_f16: gather geometry");
-    }
+// the split-K plan of a launch: K per split rounded to whole K steps, and the number of splits that leaves non-empty
+static int gemm_splits(const pt_gemm_params* q, int64_t* k_per_split) {
     int splits = q->splits < 1 ? 1 : q->splits;
-    PT_CHECK(splits == 1 || q->out_mode == 2, "pt_gemm_f16: split-K needs out_mode 2 (fp32 atomic accumulate)");
     int64_t kps = (q->K + splits - 1) / splits;
     kps = (kps + GK - 1) / GK * GK;
     if (kps < GK) kps = GK;
     splits = (int)((q->K + kps - 1) / kps);
-    if (splits < 1) splits = 1;
+    *k_per_split = kps;
+    return splits < 1 ? 1 : splits;
+}
+
+// elements of the block of memory C's addressing covers, if it covers it densely (every element once: a weight gradient in the
+// store's [T][Co][Ci] layout does); 0 otherwise
+static int64_t gemm_dense_extent(const pt_gemm_params* q) {
+    if (q->sc_m <= 0 || q->sc_n <= 0 || q->bc0 < 0 || q->bc1 < 0 || q->bc2 < 0 || q->M <= 0 || q->N <= 0 || q->nb0 < 1 || q->nb1 < 1 || q->nb2 < 1) return 0;
+    const int64_t extent = 1 + (q->M - 1) * q->sc_m + (q->N - 1) * q->sc_n + (q->nb0 - 1) * q->bc0 + (q->nb1 - 1) * q->bc1 + (q->nb2 - 1) * q->bc2;
+    return extent == (int64_t)q->M * q->N * q->nb0 * q->nb1 * q->nb2 ? extent : 0;
+}
+
+// pt_gemm_f16, and ptd_gemm_f16 (det; include/posetraj_det.h): C += alpha A B with split s's alpha * acc tile STORED to slice s of
+// the workspace [splits][C's block] and the slices added into C in ascending s by pt_fold.h - no atomics.  One split: `+=` by the
+// single writer, as out_mode 3.
+static int gemm_launch(const char* who, bool det, const pt_gemm_params* q, float* ws, int64_t ws_floats, void* stream) {
+    PT_CHECK(q && q->A && q->B && q->C, "%s: null operand", who);
+    PT_CHECK(q->M > 0 && q->N > 0 && q->K >= 0, "%s: empty problem (M %d N %d K %lld)", who, q->M, q->N, (long long)q->K);
+    PT_CHECK(q->sa_m == 1 || q->sa_k == 1, "%s: A needs a unit stride along m or k (%lld, %lld)", who, (long long)q->sa_m, (long long)q->sa_k);
+    PT_CHECK(q->sb_n == 1 || q->sb_k == 1, "%s: B needs a unit stride along n or k (%lld, %lld)", who, (long long)q->sb_n, (long long)q->sb_k);
+    PT_CHECK(q->out_mode >= 0 && q->out_mode <= 3, "%s: out_mode %d", who, q->out_mode);
+    PT_CHECK(q->nb0 >= 1 && q->nb1 >= 1 && q->nb2 >= 1, "%s: batch counts must be >= 1", who);
+    const int gather = q->g_H > 0;
+    if (gather) {
+        PT_CHECK(q->K < (1LL << 32), "%s: gather: more than 2^32 output pixels", who);
+        PT_CHECK(q->sb_n == 1, "%s: the gathered operand is channels-last (unit stride along n)", who);
+        PT_CHECK(q->g_KH >= 1 && q->g_KW >= 1 && q->nb2 == q->g_KH * q->g_KW, "%s: gather: the innermost batch runs over the %d x %d taps", who, q->g_KH, q->g_KW);
+        PT_CHECK(q->g_stride >= 1 && q->g_OH >= 1 && q->g_OW >= 1 && q->g_W >= 1, "%s: gather geometry", who);
+    }
+    int64_t kps;
+    const int splits = gemm_splits(q, &kps);
+    PT_CHECK(det || (q->splits < 1 ? 1 : q->splits) == 1 || q->out_mode == 2, "%s: split-K needs out_mode 2 (fp32 atomic accumulate)", who);
+    int out_mode = q->out_mode;
+    int64_t extent = 0;
+    if (det) {
+        PT_CHECK(q->out_mode >= 2, "%s: an accumulating product (out_mode 2 or 3)", who);
+        out_mode = 3;
+        if (splits > 1) {
+            extent = gemm_dense_extent(q);
+            PT_CHECK(extent > 0, "%s: split-K needs a C that covers one dense block of memory", who);
+            PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= splits * extent, "%s: the workspace holds %lld floats, %lld needed", who,
+                     (long long)(ws ? ws_floats : 0), (long long)(splits * extent));
+            out_mode = 1;
+        }
+    }
     GemmK k;
     k.A = Operand{(const f16*)q->A, q->sa_m, q->sa_k};
     k.B = Operand{(const f16*)q->B, q->sb_n, q->sb_k};
     k.g = Gather{gather, q->g_H, q->g_W, q->g_OH, q->g_OW, q->g_stride, q->g_pad_h, q->g_pad_w, 0, 0, q->g_ld,
                  gather ? (GK / q->g_OW) / q->g_OH : 0, gather ? (GK / q->g_OW) % q->g_OH : 0, gather ? GK % q->g_OW : 0};
     k.gKW = gather ? q->g_KW : 1;
-    k.C = q->C; k.sc_m = q->sc_m; k.sc_n = q->sc_n;
+    k.C = extent ? (void*)ws : q->C; k.sc_m = q->sc_m; k.sc_n = q->sc_n;
+    k.split_stride = extent;
     k.M = q->M; k.N = q->N; k.K = q->K; k.k_per_split = kps; k.splits = splits;
     k.nb1 = q->nb1; k.nb2 = q->nb2;
     k.ba[0] = q->ba0; k.ba[1] = q->ba1; k.ba[2] = q->ba2;
     k.bb[0] = q->bb0; k.bb[1] = q->bb1; k.bb[2] = q->bb2;
     k.bc[0] = q->bc0; k.bc[1] = q->bc1; k.bc[2] = q->bc2;
-    k.alpha = q->alpha; k.out_mode = q->out_mode;
+    k.alpha = q->alpha; k.out_mode = out_mode;
     const int64_t nz = (int64_t)q->nb0 * q->nb1 * q->nb2 * splits;
     hipStream_t s = (hipStream_t)stream;
     int tm, tn;
@@ -353,7 +388,7 @@ extern "C" int pt_gemm_f16(const pt_gemm_params* q, void* stream) {
     const int bm = 32 * tm, bn = 32 * tn;
     k.tiles_m = (q->M + bm - 1) / bm; k.tiles_n = (q->N + bn - 1) / bn;
     const int64_t nwg = (int64_t)k.tiles_m * k.tiles_n * nz;
-    PT_CHECK(nwg < (1LL << 31), "pt_gemm_f16: %lld workgroups (tiles x batch entries x splits)", (long long)nwg);
+    PT_CHECK(nwg < (1LL << 31), "%s: %lld workgroups (tiles x batch entries x splits)", who, (long long)nwg);
     const double flops = 2.0 * q->M * q->N * (double)q->K * q->nb0 * q->nb1 * q->nb2;
     pt_prof_begin(PT_PROF_GEMM, s, flops);
     const dim3 grid((unsigned)nwg, 1, 1);
@@ -376,6 +411,20 @@ extern "C" int pt_gemm_f16(const pt_gemm_params* q, void* stream) {
     else PT_GEMM_LAUNCH(4, 4);
 #undef PT_GEMM_LAUNCH
     pt_prof_end(PT_PROF_GEMM, s);
-    PT_LAUNCH_CHECK("pt_gemm_f16");
+    if (extent) launch_fold<float>(s, fold_job(ws, extent, splits, q->C, 1));
+    PT_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int pt_gemm_f16(const pt_gemm_params* q, void* stream) { return gemm_launch("pt_gemm_f16", false, q, nullptr, 0, stream); }
+
+extern "C" int64_t ptd_gemm_ws_floats(const pt_gemm_params* q) {
+    if (!q || q->M <= 0 || q->N <= 0 || q->K < 0) return 0;
+    int64_t kps;
+    const int splits = gemm_splits(q, &kps);
+    return splits > 1 ? splits * gemm_dense_extent(q) : 0;
+}
+
+extern "C" int ptd_gemm_f16(const pt_gemm_params* q, float* ws, int64_t ws_floats, void* stream) {
+    return gemm_launch("ptd_gemm_f16", true, q, ws, ws_floats, stream);
 }

@@ -14,13 +14,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.abspath(os.environ["PT_LIB"]) if os.environ.get("PT_LIB") else os.path.join(HERE, "libposetraj_hip.so")   # PT_LIB: A/B against another build on one box
 SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip"]
-HEADERS = ["pt_common.h", "igemm_tail.h"]
+HEADERS = ["pt_common.h", "igemm_tail.h", "pt_fold.h"]
 HEADER = os.path.join(HERE, "..", "include", "posetraj_hip.h")
 STRUCT_CLASSES = {"pt_igemm_params": "IgemmParams", "pt_ffn_params": "FfnParams", "pt_lnlin_params": "LnLinParams",
                   "pt_conv_f32_params": "ConvF32Params", "pt_gemm_params": "GemmParams"}
 # the optimizer extension (include/posetraj_optim.h: entry points `pto_*` of the same library, a version of its own)
 OPTIM_HEADER = os.path.join(HERE, "..", "include", "posetraj_optim.h")
 OPTIM_STRUCT_CLASSES = {"pt_adam8_segment": "Adam8Segment"}
+# the deterministic-reduction extension (include/posetraj_det.h: entry points `ptd_*`, a version of its own; it reuses pt_gemm_params)
+DET_HEADER = os.path.join(HERE, "..", "include", "posetraj_det.h")
 
 _lib = _checked = None
 
@@ -31,7 +33,7 @@ _lib = _checked = None
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _TYPE = r"(?:const\s+)?\w+\s*\*?"
 _DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
-                            | (?P<ret>%s)\s*\b(?P<fn>pto?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
+                            | (?P<ret>%s)\s*\b(?P<fn>pt[od]?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
                             | extern\s+"C"\s*\{ | \} )""" % _TYPE, re.X)
 _FIELD = re.compile(r"(%s)\s*\b(\w+(?:\s*,\s*\w+)*)" % _TYPE)         # `int32_t C0, C1`, `const void* x0`; a parameter is the one-name case
 
@@ -63,15 +65,16 @@ def _declarators(text: str, sep: str):
     return out
 
 
-def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macro: str = "PT_ABI_VERSION"):
+def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macro: str = "PT_ABI_VERSION", known_structs: dict = None):
     """(PT_ABI_VERSION, {struct tag: Structure class}, {entry point: (C return type, [C parameter types])}).  Raises on
-    anything it does not understand; no declaration is skipped.  (The messages say posetraj_hip.h for either header.)"""
+    anything it does not understand; no declaration is skipped.  (The messages say posetraj_hip.h for every header.)  ``known_structs``:
+    those of a header this one includes (they may appear in its prototypes; only its own are returned)."""
     version = re.search(r"^#define\s+%s\s+(\d+)\s*$" % version_macro, text, flags=re.M)
     if not version:
         raise ValueError(f"posetraj_hip.h: no `#define {version_macro} n`")
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
-    structs, protos, pos = {}, {}, 0
+    structs, protos, pos = dict(known_structs or {}), {}, 0
     while text[pos:].strip():
         m = _DECL.match(text, pos)
         if not m:
@@ -86,10 +89,10 @@ def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macr
             params = m.group("params").strip()
             protos[m.group("fn")] = (" ".join(m.group("ret").split()), [] if params == "void" else [t for t, _ in _declarators(params, ",")])
         pos = m.end()
-    named = re.findall(r"pto?_[a-z0-9_]+\s*\(", text)
+    named = re.findall(r"pt[od]?_[a-z0-9_]+\s*\(", text)
     if len(named) != len(protos):
         raise ValueError(f"posetraj_hip.h: {len(named)} names are followed by '(' but {len(protos)} prototypes were read")
-    return int(version.group(1)), structs, protos
+    return int(version.group(1)), {k: v for k, v in structs.items() if k not in (known_structs or {})}, protos
 
 
 with open(HEADER) as _f:
@@ -102,6 +105,9 @@ with open(OPTIM_HEADER) as _f:
 Adam8Segment = _OPTIM_STRUCTS["pt_adam8_segment"]
 OPTIM_SIGNATURES = {name: (_ctype(ret, _OPTIM_STRUCTS, returned=True), [_ctype(t, _OPTIM_STRUCTS) for t in params])
                     for name, (ret, params) in OPTIM_PROTOTYPES.items()}
+with open(DET_HEADER) as _f:
+    DET_ABI_VERSION, _, DET_PROTOTYPES = _parse_header(_f.read(), {}, "PT_DET_ABI_VERSION", _STRUCTS)
+DET_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in DET_PROTOTYPES.items()}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -112,7 +118,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -189,7 +195,7 @@ def source_digest() -> str:
     to replay them for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER]):
+    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER]):
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
     return h.hexdigest()
@@ -203,15 +209,15 @@ def _load(errcheck=None):
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(posetraj_amd has no CPU or PyTorch fallback path)")
     L = C.CDLL(LIB_PATH)
-    for sigs, protos in ((SIGNATURES, PROTOTYPES), (OPTIM_SIGNATURES, OPTIM_PROTOTYPES)):
+    for sigs, protos in ((SIGNATURES, PROTOTYPES), (OPTIM_SIGNATURES, OPTIM_PROTOTYPES), (DET_SIGNATURES, DET_PROTOTYPES)):
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)            # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
-            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version"):
+            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version", "ptd_abi_version"):
                 fn.errcheck = errcheck
-    if L.pt_abi_version() != ABI_VERSION or L.pto_abi_version() != OPTIM_ABI_VERSION:
-        raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} / optimizer extension {L.pto_abi_version()} != expected "
-                           f"{ABI_VERSION} / {OPTIM_ABI_VERSION}; rebuild")
+    if L.pt_abi_version() != ABI_VERSION or L.pto_abi_version() != OPTIM_ABI_VERSION or L.ptd_abi_version() != DET_ABI_VERSION:
+        raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} / optimizer extension {L.pto_abi_version()} / deterministic extension "
+                           f"{L.ptd_abi_version()} != expected {ABI_VERSION} / {OPTIM_ABI_VERSION} / {DET_ABI_VERSION}; rebuild")
     return L
 
 

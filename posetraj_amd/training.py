@@ -244,6 +244,19 @@ class ControlNetTrainer:
     ``use_8bit_adam``, data parallel and the side streams are untouched - the segments' weight gradients and ``grad_ready`` calls
     happen in the same order, once per micro-batch - and a checkpoint file knows nothing of the mode.  Not with ``use_graph``.
 
+    ``deterministic`` (the script's ``--seed`` "for reproducible training" made to hold): ``False`` (the default) is the step as it was,
+    launch for launch - its reverse pass accumulates with fp32 atomics, so two identical steps differ in the last bits.  ``True``: the
+    gradients, the losses, ``grad_norm()`` and the parameters after ``optimizer_step()`` are a pure function of the trainer's inputs
+    and state, on one GPU and for one build of the library - whatever the workgroup scheduling, whichever side streams are live (the
+    first step of a fresh trainer and a later one agree), under every ``gradient_checkpointing`` mode (whose gradients then EQUAL the
+    plain step's), under accumulation, ``use_ema`` and ``use_8bit_adam``.  Every reduction of the reverse pass that used atomics -
+    GroupNorm's statistics and parameter gradients, LayerNorm's parameter gradients, bias / row-vector column sums, the AlphaBlender's
+    ``mix_factor`` gradient, the gradient norm, split-K weight gradients - runs in two launches instead (``include/posetraj_det.h``): the
+    same kernel storing one partial per workgroup into a workspace of its own, and a fold that adds them in ascending order; no atomics,
+    no waiting between workgroups.  The forward and the attention backward were bit-reproducible already.  Under ``torch.distributed``
+    the flag is accepted, but nothing is claimed across ranks: the all-reduce's order is the collective library's.  Nor across library
+    builds or tile-plan changes.  A checkpoint file knows nothing of the mode.  Not with ``use_graph``.  Cost: DESIGN 4.13.
+
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
 
@@ -255,7 +268,7 @@ class ControlNetTrainer:
                  lr_scheduler=None, use_graph: bool = False, device_scalars: Optional[bool] = None, encoder_stream: bool = True,
                  pack_stream: bool = True, use_ema: bool = False, ema_decay: float = 0.9999, ema_min_decay: float = 0.0,
                  ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3,
-                 use_8bit_adam: bool = False, gradient_checkpointing=False):
+                 use_8bit_adam: bool = False, gradient_checkpointing=False, deterministic: bool = False):
         from . import autodiff as AD
         from . import grad_sync
         from . import train_graph as TG
@@ -268,12 +281,16 @@ class ControlNetTrainer:
             raise ValueError("ControlNetTrainer(use_graph=True) does not take gradient_checkpointing: the captured step exists to cut host "
                              "time, which the recomputation's launches add to, and it holds its buffers in one pool for the graph's "
                              "lifetime anyway, so dropping activations frees nothing")
+        if use_graph and deterministic:
+            raise ValueError("ControlNetTrainer(use_graph=True) does not take deterministic=True: the deterministic reductions take a workspace "
+                             "per call from the allocator of the calling stream, and the captured step is out of the mode's scope")
         self.gradient_checkpointing = gradient_checkpointing
         self._ckpt_cn, self._ckpt_dec = bool(gradient_checkpointing), gradient_checkpointing == "all"
         cfg = dict(controlnet_config)
         self.unet, self.device, self.config = unet, dev, cfg
         self.use_8bit_adam = bool(use_8bit_adam)
         self.params = AD.ParamStore(controlnet_state_dict, dev, use_8bit_adam=self.use_8bit_adam)
+        self.deterministic = self.params.deterministic = bool(deterministic)
         self.controlnet = TG.ControlNetGraph(self.params, cfg)
         self._frozen = AD.FrozenParams({k: v for k, v in unet.state_dict().items() if k.startswith(("up_blocks.", "conv_norm_out.", "conv_out."))}, dev)
         self.decoder = TG.UNetDecoderGraph(self._frozen, dict(unet.config))
@@ -500,6 +517,7 @@ class ControlNetTrainer:
             self._side = torch.cuda.Stream()
         AD.WGRAD_STREAM = self._side if self.wgrad_stream else None
         self.buckets.streams = [main, AD.WGRAD_STREAM]
+        AD.DETERMINISTIC = self.params.deterministic         # (every reduction with atomics lies in the reverse pass: the tapes' closures)
         try:
             if use_spatial:                                   # the frozen decoder has no weight gradients: nothing of this pass leaves its stream
                 with torch.cuda.stream(spatial_stream) if spatial_stream is not None else _null():
@@ -511,7 +529,7 @@ class ControlNetTrainer:
                 AD.add_rows(x_, r0_, r1_, dy_)
             tape_cn.backward()
         finally:
-            AD.WGRAD_STREAM = None
+            AD.WGRAD_STREAM, AD.DETERMINISTIC = None, False
         if self.wgrad_stream:
             main.wait_stream(self._side)                      # every weight gradient is in before anyone reads the buffer
         if sync:
@@ -526,7 +544,12 @@ class ControlNetTrainer:
     def grad_norm(self) -> float:
         """Global L2 norm of the (un-scaled) gradients; ``inf`` / ``nan`` when an fp16 gradient overflowed."""
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        hip.checked().pt_sumsq_f32(self.params.grad.data_ptr(), self.params.numel, acc.data_ptr(), ops._stream())
+        L, P = hip.checked(), self.params
+        if P.deterministic:
+            ws = torch.empty(L.ptd_sumsq_ws_floats(P.numel), dtype=torch.float32, device=self.device)
+            L.ptd_sumsq_f32(P.grad.data_ptr(), P.numel, acc.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+        else:
+            L.pt_sumsq_f32(P.grad.data_ptr(), P.numel, acc.data_ptr(), ops._stream())
         return math.sqrt(float(acc)) / ((self._accum_scale or 1.0) * self.world) if math.isfinite(float(acc)) else float(acc)
 
     def optimizer_step(self, grad_norm: Optional[float] = None) -> bool:

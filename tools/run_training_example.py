@@ -34,6 +34,7 @@ ap.add_argument("--use-ema", action="store_true"); ap.add_argument("--validation
 ap.add_argument("--graph", action="store_true", help="ControlNetTrainer(use_graph=True): the step replayed as a hipGraph (needs --accumulation 1)")
 ap.add_argument("--gradient-checkpointing", choices=("off", "controlnet", "all"), default="off",
                 help="controlnet: the reference's --gradient_checkpointing (:1025-1026), ControlNetTrainer(gradient_checkpointing=True); all: the frozen decoder's blocks too")
+ap.add_argument("--deterministic", action="store_true", help="ControlNetTrainer(deterministic=True): bit-reproducible gradients (the script's --seed made to hold)")
 a = ap.parse_args()
 from posetraj_amd import train_state
 dev = torch.device("cuda:0")
@@ -56,7 +57,7 @@ else:
     controlnet = ControlNetSDVModel.from_unet(unet, conditioning_embedding_out_channels=ce)                      # :935-938
 max_train_steps = max(1, a.steps // a.accumulation)
 trainer = ControlNetTrainer(controlnet.config, controlnet.state_dict(), unet, learning_rate=1e-5, freeze_gc=True, gradient_accumulation_steps=a.accumulation, use_graph=a.graph, use_ema=a.use_ema,
-                            gradient_checkpointing={"off": False, "controlnet": True, "all": "all"}[a.gradient_checkpointing],
+                            gradient_checkpointing={"off": False, "controlnet": True, "all": "all"}[a.gradient_checkpointing], deterministic=a.deterministic,
                             conditioning_dropout_prob=0.1, scaling_factor=vae.config.scaling_factor,
                             lr_scheduler=train_state.get_scheduler(a.lr_scheduler, a.lr_warmup_steps, max_train_steps, lr_init=1e-5))    # :1109-1114
 global_step, first_it = 0, 0

@@ -5,7 +5,7 @@ of the three families (pt_igemm_f16: forward and data gradients; pt_gemm_f16: we
 the memory high-water mark.
 
     python tools/train_step_bench.py [--steps 5] [--height 320 --width 576] [--frames 14] [--tiny] [--gemm-table] [--igemm-table]
-        [--temporal-bwd fused|recompute] [--optimizer adamw|adamw8bit] [--gradient-checkpointing off|controlnet|all]
+        [--temporal-bwd fused|recompute] [--optimizer adamw|adamw8bit] [--gradient-checkpointing off|controlnet|all] [--deterministic]
     python tools/train_step_bench.py --optimizer-launch 3          # the optimizer's launch alone at the full parameter count: pt_adamw_fused_f32
         against pto_adamw8_f32 (and their EMA forms), that many interleaved rounds
     python tools/train_step_bench.py --json --steps 7 --warmup 3      # what bench.py --train-step runs as a child process:
@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--gradient-checkpointing", choices=("off", "controlnet", "all"), default="off",
                     help="ControlNetTrainer(gradient_checkpointing=...): controlnet = True (the reference's --gradient_checkpointing: the ControlNet's "
                          "blocks are recomputed in the reverse pass), all = the frozen decoder's blocks too")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="ControlNetTrainer(deterministic=True): the reverse pass's reductions in two launches over a workspace (ptd_*), no atomics")
     ap.add_argument("--optimizer-launch", type=int, default=0, metavar="ROUNDS",
                     help="time the optimizer launches alone over the ControlNet's parameter inventory (no network is built) and exit")
     ap.add_argument("--json", action="store_true", help="bench.py's train_step leg: time the steps without hipEvent brackets (median), count the matrix "
@@ -77,7 +79,7 @@ def main():
     tr = ControlNetTrainer(ccfg, sd, unet, learning_rate=1e-5, conditioning_dropout_prob=0.1, freeze_gc=True, use_graph=a.graph,
                            wgrad_stream=not a.no_wgrad_stream, encoder_stream=not a.no_encoder_stream, spatial_stream=not a.no_spatial_stream, pack_stream=not a.no_pack_stream,
                            use_ema=a.ema != "off", use_8bit_adam=a.optimizer == "adamw8bit",
-                           gradient_checkpointing={"off": False, "controlnet": True, "all": "all"}[a.gradient_checkpointing])
+                           gradient_checkpointing={"off": False, "controlnet": True, "all": "all"}[a.gradient_checkpointing], deterministic=a.deterministic)
     tr.ema_fused = a.ema != "separate"
     moments = "2 Adam moments" if tr.params.adam8 is None else f"8-bit Adam state, {tr.params.adam8.plan['state_bytes'] / 2 ** 20:.0f} MiB"
     print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + {moments}"
@@ -135,7 +137,7 @@ def main():
                           "trainable_params_M": round(tr.params.numel / 1e6, 1), "loss_finite": bool(out["loss"] == out["loss"]),
                           "optimizer_stepped": bool(out["stepped"]), "hipgraph": bool(a.graph), "step_graphs": n_graphs,
                           "graph_replays_in_timed_steps": int(sum(replayed)), **({"ema": a.ema} if a.ema != "off" else {}), **({"optimizer": a.optimizer} if a.optimizer != "adamw" else {}),
-                          **({"gradient_checkpointing": a.gradient_checkpointing} if a.gradient_checkpointing != "off" else {}),
+                          **({"gradient_checkpointing": a.gradient_checkpointing} if a.gradient_checkpointing != "off" else {}), **({"deterministic": True} if a.deterministic else {}),
                           "host_gc_in_timed_steps": [g for g in gc_log if g[1] >= 1.0], "streams": 1 + int(tr.wgrad_stream) + int(tr.spatial_stream and not a.no_spatial) + int(tr.encoder_stream)}))
         return
     L.pt_prof_enable(1)
