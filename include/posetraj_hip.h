@@ -233,7 +233,8 @@ int pt_layernorm_f16(const void* x, int64_t M, int32_t C, const void* vec, int32
  * qkv is the fused projection output [Nimg*S, ld] with Q at column h*64, K at k_off + h*64, V at v_off + h*64.
  * Replaces F.scaled_dot_product_attention in BasicTransformerBlock.attn1 (AttnProcessor2_0).
  * Temporal self-attention over the frame axis: tokens of one sequence are the F rows (b, f, s), f = 0..F-1, of
- * the same matrix, F <= 32 (two 16-frame blocks above 16: SVD-XT and the in-tree default num_frames = 25).  Replaces SDPA in TemporalBasicTransformerBlock.attn1 (models/modified_svd.py:79-81)
+ * the same matrix, 1 <= F <= 128 (blocks of 16 frames: one, two - SVD-XT and the in-tree default num_frames = 25 - or, from 33 frames
+ * on, three to eight with K and V staged in LDS; the entry point and PT_ABI_VERSION are unchanged by the wider range).  Replaces SDPA in TemporalBasicTransformerBlock.attn1 (models/modified_svd.py:79-81)
  * together with the two permute/reshape copies around it (:64-66, :110-112).
  * --------------------------------------------------------------------------------------------------------- */
 /* q_prescaled = 1: the Q columns already carry scale * log2(e) (cs_cols / cs_scale of the projection's pt_igemm_f16
@@ -408,7 +409,8 @@ int pt_attn_bwd_f16(const void* q, int32_t ldq, const void* k, int32_t ldk, cons
                     int32_t ldout, const void* dout, int32_t ldo, const float* lse, float* dq_dot, void* dq, void* dk, void* dv,
                     int32_t ldd, int32_t nbatch, int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream);
 /* backward of pt_attn_temporal_f16 (same addressing: token f of (clip b, position s) is row (b F + f) S + s of the fused
- * projection) for F <= 32 frames: dqkv gets dQ | dK | dV at the offsets 0 / k_off / v_off of its rows (pitch ldd). */
+ * projection) for F <= 32 frames: dqkv gets dQ | dK | dV at the offsets 0 / k_off / v_off of its rows (pitch ldd).
+ * 33 .. 128 frames: ptt_attn_temporal_bwd_long_f16 of include/posetraj_temporal.h. */
 int pt_attn_temporal_bwd_f16(const void* qkv, int32_t ld, int32_t k_off, int32_t v_off, const void* dout, int32_t ldo, void* dqkv,
                              int32_t ldd, int32_t B, int32_t F, int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream);
 /* backward of pt_groupnorm_stats + pt_groupnorm_apply (same argument meaning; two channels-last sources): dy [rows, C0 + C1]

@@ -853,6 +853,7 @@ def _one_key_backward(qkv: torch.Tensor, dout: torch.Tensor, Cc: int) -> torch.T
 ATTN_SCORE_BYTES = 2 << 30          # score-matrix memory (fp32) the recomputing attention backward holds at a time
 FLASH_BACKWARD = True               # spatial attention: pt_attn_fwd_lse_f16 / pt_attn_bwd_f16 (False: recompute through pt_gemm_f16)
 TEMPORAL_FLASH_FRAMES = 32          # temporal attention: clips up to this many frames take pt_attn_temporal_bwd_f16 (16: longer ones recompute)
+TEMPORAL_LONG_BACKWARD = True       # temporal attention, 33 - 128 frames: ptt_attn_temporal_bwd_long_f16 (False: recompute through pt_gemm_f16)
 
 
 def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> Var:
@@ -895,9 +896,11 @@ def attn_spatial(tape: Tape, qkv: Var, N: int, S: int, heads: int, hd: int) -> V
 
 def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: int) -> Var:
     """Self-attention over the F frames of each spatial position; token f of (clip b, position s) is row (b F + f) S + s.
-    Backward: one frame is the exact shortcut; up to ``TEMPORAL_FLASH_FRAMES`` frames (32, what the kernel covers: one block of 16
-    frames per wave, two above 16) at head sizes 64 / 128 the one-launch ``pt_attn_temporal_bwd_f16``; everything else recomputes
-    the scores through ``_attention_backward``."""
+    The forward takes 1 .. 128 frames.  Backward: one frame is the exact shortcut; up to ``TEMPORAL_FLASH_FRAMES`` frames (32, what
+    that kernel covers: one block of 16 frames per wave, two above 16) at head sizes 64 / 128 the one-launch
+    ``pt_attn_temporal_bwd_f16``; 33 .. 128 frames at those head sizes the one-launch ``ptt_attn_temporal_bwd_long_f16`` (two sweeps
+    over operands staged in LDS) while ``TEMPORAL_LONG_BACKWARD`` is set; everything else recomputes the scores through
+    ``_attention_backward``."""
     Cc = heads * hd
     out = Var(ops.attn_temporal(qkv.v, B, F, S, heads, hd))
 
@@ -909,6 +912,12 @@ def attn_temporal(tape: Tape, qkv: Var, B: int, F: int, S: int, heads: int, hd: 
             dqkv = torch.empty_like(qkv.v)
             hip.checked().pt_attn_temporal_bwd_f16(qkv.v.data_ptr(), qkv.v.stride(0), Cc, 2 * Cc, dy.data_ptr(), dy.stride(0), dqkv.data_ptr(),
                                                    dqkv.stride(0), B, F, S, heads, hd, hd ** -0.5, _stream())
+            _acc(qkv, dqkv)
+            return
+        if FLASH_BACKWARD and TEMPORAL_LONG_BACKWARD and 32 < F <= 128 and hd in (64, 128):
+            dqkv = torch.empty_like(qkv.v)
+            hip.checked().ptt_attn_temporal_bwd_long_f16(qkv.v.data_ptr(), qkv.v.stride(0), Cc, 2 * Cc, dy.data_ptr(), dy.stride(0), dqkv.data_ptr(),
+                                                         dqkv.stride(0), B, F, S, heads, hd, hd ** -0.5, _stream())
             _acc(qkv, dqkv)
             return
         _acc(qkv, _attention_backward(qkv.v, dy, Cc, heads, hd, F, S, (B, F * S, S, 1), 1))

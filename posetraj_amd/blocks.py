@@ -7,7 +7,7 @@ Each class mirrors one diffusers==0.24.0 block the reference instantiates (``mod
 
 * spatial ops see the token matrix ``[N*H*W, C]``;
 * temporal convolutions see an image ``(H', W') = (F, H*W)`` with a (3 x 1) kernel over the same memory;
-* temporal attention reads its F tokens with a row stride of ``H*W`` (``pt_attn_temporal_f16``);
+* temporal attention reads its F tokens (1 .. 128 frames) with a row stride of ``H*W`` (``pt_attn_temporal_f16``);
 * the skip concatenation of the up blocks is a 2-source gather inside the convolution.
 
 Work that provably does not depend on the activations is hoisted out of the blocks:

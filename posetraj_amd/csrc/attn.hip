@@ -8,9 +8,10 @@
 //   (the threshold test is a wave-wide OR of lane-local maxima, the row sum an MFMA against ones); the exponentiated accumulators
 //   are, after a pairwise fp16 convert, directly the B operand of O^T += V^T P^T (the k order inside a step is the accumulators' row
 //   order, V^T is fetched with ds_read_b64_tr_b16 in that same order).  O^T leaves through an LDS transpose as 16-byte row stores.
-// pt_attn_temporal_f16 : attention over the <=16 frames of one spatial position (HBM-bound, 0.05 % of the flops):
-//   one wave per (clip, position, head), scores and PV on the matrix cores (v_mfma_f32_16x16x32_f16 / 16x16x16),
-//   operands as (frame, 8 channels) fragments straight from global memory; details at the kernel.
+// pt_attn_temporal_f16 : attention over the 1 .. 128 frames of one spatial position (HBM-bound, 0.05 % of the flops at 14 frames):
+//   one wave per (clip, position, head), scores and PV on the matrix cores (v_mfma_f32_16x16x32_f16 / 16x16x16);
+//   up to 32 frames the operands are (frame, 8 channels) fragments straight from global memory, 33 .. 128 frames stage K and V in
+//   the wave's LDS slab and loop over query blocks; details at the kernels.
 #include "pt_common.h"
 #include <stdlib.h>
 
@@ -267,7 +268,8 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
 // cores.  (The first version did the 14 x 14 x 64 products on the VALU, ~1000 instructions per task, and ran
 // VALU-bound at 2.6-2.7 TB/s; this one is ~150 VALU + 6 MFMAs and streams at the HBM rate.)
 // Frames come in NB blocks of 16: NB = 1 for F <= 16 (SVD: 14), NB = 2 for F <= 32 (SVD-XT and the reference's in-tree
-// default num_frames = 25, /root/reference/models/controlnet_sdv.py:263).  Per (key block kb, query block qb):
+// default num_frames = 25, /root/reference/models/controlnet_sdv.py:263); 33 .. 128 frames: attn_temporal_long_kernel below.
+// Per (key block kb, query block qb):
 //   S^T = K Q^T   : 2 x v_mfma_f32_16x16x32_f16; both operands are (frame = 16 blk + (lane & 15), 8 consecutive d)
 //                   fragments loaded straight from global memory (16 B per lane, frames >= F read as zero)
 //   softmax over the key frame k = 16 kb + 4 (lane >> 4) + j: in-lane over (kb, j), then two cross-lane steps (xor 16, 32)
@@ -367,6 +369,122 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const f16* __restric
     }
 }
 
+// Clips of 33 .. 128 frames: NB = 3 .. 8 blocks of 16 frames.  The [NB][NB] fragment arrays of the kernel above do not fit the
+// register file at NB = 8, so this one keeps the task mapping (one wave per (clip, position, head), the same MFMA shapes and
+// accumulator layouts, the same rounding points) and changes where the operands live:
+//   K, V  : the task's rows are read from HBM once (16-byte chunks, frames >= F as zero) and staged in the wave's LDS slab as
+//           [16 NB][HDIM] rows at a pitch of 2 HDIM + 32 bytes; the K fragments are ds_read_b128 row reads, V^T comes through
+//           ds_read_b64_tr_b16 (the transposed read of attn_temporal_bwd2_kernel, csrc/attn_bwd.hip)
+//   Q     : one block of 16 frames at a time, fragments straight from global memory, the next block's under this one's math
+//   scores: one query block against ALL keys is NB x 4 floats per lane, so the row maximum is taken over every key block in
+//           registers and the softmax is exact - no online rescaling; P is rounded to fp16 once, the sum is that of the fp32 P,
+//           1 / sum is applied to the fp32 output, one fp16 store
+// LDS per wave: 2 x 16 NB x (2 HDIM + 32) bytes = 15 KiB (NB = 3, HDIM 64) .. 72 KiB (NB = 8, HDIM 128); temporal_long_waves picks
+// 4, 2 or 1 waves per workgroup so that two workgroups fit a CU's 160 KiB where one slab allows it.  No workgroup-level
+// synchronisation: a wave only ever reads its own slab (wave barrier after its own writes).
+constexpr int TFL_MAX = 128;
+constexpr int temporal_long_waves(int slab_bytes) { return 4 * slab_bytes <= 80 * 1024 ? 4 : 2 * slab_bytes <= 80 * 1024 ? 2 : 1; }
+
+template <int NB, int HDIM, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void attn_temporal_long_kernel(const f16* __restrict__ qkv, int ld, int k_off, int v_off,
+                                                                        f16* __restrict__ out, int ldo, int F, int S, int heads,
+                                                                        int64_t ntasks, float scale) {
+    constexpr int NS = HDIM / 32;                            // 32-deep steps of the score product
+    constexpr int PITCH = 2 * HDIM + 32;                     // bytes per staged row
+    constexpr int ROWS = 16 * NB;
+    constexpr int CH = HDIM / 8;                             // 16-byte chunks per row
+    constexpr int NV = 16 * CH / 64;                         // chunks per lane and block of 16 frames
+    __shared__ __attribute__((aligned(16))) char smem[WAVES * 2 * ROWS * PITCH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t task = (int64_t)blockIdx.x * WAVES + wave;
+    if (task >= ntasks) return;                              // whole waves only: EXEC stays full for the transposed reads
+    const int head = (int)(task % heads);
+    const int64_t bs = task / heads;
+    const int s = (int)(bs % S);
+    const int64_t b = bs / S;
+    const int c = lane & 15, g = lane >> 4;
+    char* const Ks = smem + wave * (2 * ROWS * PITCH);
+    char* const Vs = Ks + ROWS * PITCH;
+    const f16x8 zero8 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+    const f16* const base = qkv + head * HDIM;               // + row * ld
+    // ---- K and V rows -> LDS (frames >= F as zero: their scores are masked, their P is 0, and 0 x 0 stays 0)
+#pragma unroll 8 / NV                                       // 16 loads of 16 bytes per lane in flight, not 16 NB
+    for (int blk = 0; blk < NB; ++blk) {
+        f16x8 kr[NV], vr[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = lane + 64 * i, f = 16 * blk + idx / CH;
+            const f16* p = base + ((b * F + (f < F ? f : 0)) * (int64_t)S + s) * ld + (idx % CH) * 8;
+            kr[i] = f < F ? *(const f16x8*)(p + k_off) : zero8;
+            vr[i] = f < F ? *(const f16x8*)(p + v_off) : zero8;
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = lane + 64 * i, at = (16 * blk + idx / CH) * PITCH + (idx % CH) * 16;
+            *(f16x8*)(Ks + at) = kr[i];
+            *(f16x8*)(Vs + at) = vr[i];
+        }
+    }
+    // Q fragments of a block: lane (c, g) holds Q[16 qb + c][32 h + 8 g .. + 7]
+    auto load_q = [&](int qb, f16x8 (&q)[NS]) {
+        const int f = 16 * qb + c;
+        const f16* p = base + ((b * F + (f < F ? f : 0)) * (int64_t)S + s) * ld + g * 8;
+#pragma unroll
+        for (int h = 0; h < NS; ++h) q[h] = f < F ? *(const f16x8*)(p + 32 * h) : zero8;
+    };
+    f16x8 qn[NS];
+    load_q(0, qn);
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));               // this wave's K and V rows are in LDS
+    __builtin_amdgcn_wave_barrier();
+    const int kr0 = c * PITCH + 16 * g;                      // row read: row c, chunk g of a 32-channel step
+    const int tr = (4 * g + (c >> 2)) * PITCH + 8 * (c & 3); // transposed read: element j = row 4 g + j, column c of a 16-channel block
+#pragma unroll 1
+    for (int qb = 0; qb < NB; ++qb) {
+        f16x8 qf[NS];
+#pragma unroll
+        for (int h = 0; h < NS; ++h) qf[h] = qn[h];
+        if (qb + 1 < NB) load_q(qb + 1, qn);
+        // ---- S^T[k][q] against every key block  (lane: k = 16 kb + 4 g + j, q = 16 qb + c)
+        float p[NB][4], mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb) {
+            f32x4 st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int h = 0; h < NS; ++h)
+                st = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(Ks + kr0 + 16 * kb * PITCH + 64 * h), qf[h], st, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                p[kb][j] = (16 * kb + 4 * g + j < F) ? st[j] * scale : -INFINITY;
+                mx = fmaxf(mx, p[kb][j]);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float sum = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { p[kb][j] = __expf(p[kb][j] - mx); sum += p[kb][j]; }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        f16x4 pt[NB];
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb) pt[kb] = (f16x4){(f16)p[kb][0], (f16)p[kb][1], (f16)p[kb][2], (f16)p[kb][3]};
+        // ---- O^T[d][q] = sum_k V[k][d] P^T[k][q]
+        const int f = 16 * qb + c;
+        f16* const op = out + ((b * F + (f < F ? f : 0)) * (int64_t)S + s) * ldo + head * HDIM + 4 * g;
+#pragma unroll
+        for (int blk = 0; blk < HDIM / 16; ++blk) {
+            f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < NB; ++kb)
+                o = __builtin_amdgcn_mfma_f32_16x16x16f16(pt_lds_tr16(Vs + tr + 16 * kb * PITCH + 32 * blk), pt[kb], o, 0, 0, 0);
+            if (f < F) *(f16x4*)(op + 16 * blk) = (f16x4){(f16)(o[0] * inv), (f16)(o[1] * inv), (f16)(o[2] * inv), (f16)(o[3] * inv)};
+        }
+    }
+}
+
 }  // namespace
 
 namespace { int g_attn_nqb = 3; }
@@ -410,10 +528,32 @@ extern "C" int pt_attn_temporal_f16(const void* qkv, int32_t ld, int32_t k_off, 
                                     void* stream) {
     PT_CHECK(qkv && out, "pt_attn_temporal_f16: null pointer");
     PT_CHECK(head_dim == 64 || head_dim == 128, "pt_attn_temporal_f16: head_dim %d unsupported (64, 128)", head_dim);
-    PT_CHECK(F >= 1 && F <= TF_MAX, "pt_attn_temporal_f16: %d frames unsupported (1..32)", F);
+    PT_CHECK(F >= 1 && F <= TFL_MAX, "pt_attn_temporal_f16: %d frames unsupported (1..128)", F);
     PT_CHECK(ld % 8 == 0 && ldo % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0, "pt_attn_temporal_f16: pitches/offsets must be multiples of 8");
     const int64_t ntasks = (int64_t)B * S * heads;
     PT_CHECK(ntasks > 0 && (ntasks + 3) / 4 < (1ll << 31), "pt_attn_temporal_f16: bad sizes");
+    if (F > TF_MAX) {                                        // 3 .. 8 blocks of 16 frames: attn_temporal_long_kernel
+        PT_CHECK(ntasks < (1ll << 31), "pt_attn_temporal_f16: grid too large");
+#define PT_TATTN_LONG(NB_, HD_)                                                                                                           \
+    do {                                                                                                                                  \
+        constexpr int W_ = temporal_long_waves(2 * 16 * NB_ * (2 * HD_ + 32));                                                            \
+        hipLaunchKernelGGL((attn_temporal_long_kernel<NB_, HD_, W_>), dim3((unsigned)((ntasks + W_ - 1) / W_)), dim3(64 * W_), 0,         \
+                           (hipStream_t)stream, (const f16*)qkv, ld, k_off, v_off, (f16*)out, ldo, F, S, heads, ntasks, scale);           \
+    } while (0)
+#define PT_TATTN_LONG_HD(NB_) do { if (head_dim == 64) PT_TATTN_LONG(NB_, 64); else PT_TATTN_LONG(NB_, 128); } while (0)
+        switch ((F + 15) / 16) {
+            case 3: PT_TATTN_LONG_HD(3); break;
+            case 4: PT_TATTN_LONG_HD(4); break;
+            case 5: PT_TATTN_LONG_HD(5); break;
+            case 6: PT_TATTN_LONG_HD(6); break;
+            case 7: PT_TATTN_LONG_HD(7); break;
+            default: PT_TATTN_LONG_HD(8); break;
+        }
+#undef PT_TATTN_LONG_HD
+#undef PT_TATTN_LONG
+        PT_LAUNCH_CHECK("pt_attn_temporal_f16");
+        return 0;
+    }
     const dim3 grid((unsigned)((ntasks + 3) / 4));
 #define PT_TATTN(NB_, HD_)                                                                                                    \
     hipLaunchKernelGGL((attn_temporal_kernel<NB_, HD_>), grid, dim3(256), 0, (hipStream_t)stream, (const f16*)qkv, ld, k_off,  \

@@ -19,7 +19,10 @@
 //
 // The temporal attentions (F <= 32 frames of one spatial position) need neither passes nor a stored log-sum-exp: one wave holds
 // the whole F x F problem.  attn_temporal_bwd_kernel: F <= 16 (one block of 16 frames); attn_temporal_bwd2_kernel: 17 .. 32 (two).
+// 33 .. 128 frames (attn_temporal_bwd_long_kernel, three to eight blocks): still one wave per problem and one launch, but as the two
+// passes above in miniature - a query-stationary and a key-stationary sweep over rows staged in the wave's LDS slab.
 #include "pt_common.h"
+#include "../../include/posetraj_temporal.h"
 
 namespace {
 
@@ -570,6 +573,200 @@ __global__ __launch_bounds__(64 * WAVES) void attn_temporal_bwd2_kernel(const f1
     }
 }
 
+// The same for 33 <= F <= 128 frames: NB = 3 .. 8 blocks of 16 frames (ptt_attn_temporal_bwd_long_f16, include/posetraj_temporal.h).
+// Fp32 dK / dV accumulators of 128 frames x 128 channels do not fit one wave beside the rest, so the task is swept twice over
+// operands staged in the wave's LDS slab ([16 NB][HDIM] rows at the pitch above, frames >= F as zero) - the structure of the
+// spatial passes at the top of this file, inside one wave and one launch:
+//   sweep 1, query-stationary (LDS: K, V rows; Q / dO fragments of one query block from global memory): the scores against ALL keys
+//     in orientation b (rows k = 16 kb + 4 g + i, column q = 16 qb + c) are NB x 4 floats per lane, so softmax, dP, the row term
+//     sum_k P dP and dS are exact in registers; dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q] through transposed reads of the K rows.
+//     Row maximum, row sum and sum_k P dP of every query go to 3 x 16 NB floats of the slab.
+//   sweep 2, key-stationary (the SAME slab, now Q and dO rows; K / V fragments of one key block from global memory): orientation a
+//     (rows q = 16 qb + 4 g + i, column k = 16 kb + c), P recomputed from the saved row statistics with the expression of sweep 1,
+//     dV^T[d][k] = sum_q dO^T[d][q] P[q][k] and dK^T[d][k] = sum_q Q^T[d][q] dS[q][k] accumulate over the query blocks in registers.
+// Same rounding points as the kernels above (P and dS to fp16 once, fp32 accumulation, one fp16 store per gradient element).
+// Every gradient element is written by exactly one lane of one wave: no atomics, nothing crosses waves, the result does not
+// depend on scheduling.  LDS per wave: 2 x 16 NB x (2 HDIM + 32) + 192 NB bytes (15.6 KiB .. 73.5 KiB); temporal_bwd_long_waves
+// picks 4, 2 or 1 waves per workgroup so that two workgroups fit a CU's 160 KiB where one slab allows it.
+constexpr int temporal_bwd_long_slab(int nb, int hdim) { return 2 * 16 * nb * (2 * hdim + 32) + 3 * 16 * nb * 4; }
+constexpr int temporal_bwd_long_waves(int slab_bytes) { return 4 * slab_bytes <= 80 * 1024 ? 4 : 2 * slab_bytes <= 80 * 1024 ? 2 : 1; }
+
+template <int NB, int HDIM, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void attn_temporal_bwd_long_kernel(const f16* __restrict__ qkv, int ld, int k_off, int v_off,
+                                                                            const f16* __restrict__ dout, int ldo, f16* __restrict__ dqkv, int ldd,
+                                                                            int F, int S, int heads, int64_t ntasks, float scale) {
+    constexpr int NS = HDIM / 32;
+    constexpr int PITCH = 2 * HDIM + 32;                                  // bytes per staged row
+    constexpr int ROWS = 16 * NB;
+    constexpr int CH = HDIM / 8;                                          // 16-byte chunks per row
+    constexpr int NV = 16 * CH / 64;                                      // chunks per lane and block of 16 frames
+    constexpr int SLAB = temporal_bwd_long_slab(NB, HDIM);
+    __shared__ __attribute__((aligned(16))) char smem[WAVES * SLAB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t task = (int64_t)blockIdx.x * WAVES + wave;
+    if (task >= ntasks) return;                                           // whole waves only: EXEC stays full for the transposed reads
+    const int head = (int)(task % heads);
+    const int64_t bs = task / heads;
+    const int s = (int)(bs % S);
+    const int64_t b = bs / S;
+    const int c = lane & 15, g = lane >> 4;
+    char* const As = smem + wave * SLAB;                                  // sweep 1: K rows, sweep 2: Q rows
+    char* const Bs = As + ROWS * PITCH;                                   // sweep 1: V rows, sweep 2: dO rows
+    float* const Ms = (float*)(Bs + ROWS * PITCH);                        // per query: row maximum, row sum, sum_k P dP
+    float* const Zs = Ms + ROWS;
+    float* const Ds = Zs + ROWS;
+    const f16x8 zero8 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    auto row_of = [&](int f) { return (b * F + (f < F ? f : 0)) * (int64_t)S + s; };
+    // rows of two operands -> As / Bs (frames >= F as zero)
+    auto stage = [&](const f16* pa_, int lda, const f16* pb_, int ldb) {
+#pragma unroll 8 / NV                                                    // 16 loads of 16 bytes per lane in flight, not 16 NB
+        for (int blk = 0; blk < NB; ++blk) {
+            f16x8 ar[NV], br[NV];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int idx = lane + 64 * i, f = 16 * blk + idx / CH;
+                const int64_t row = row_of(f);
+                ar[i] = f < F ? *(const f16x8*)(pa_ + row * lda + (idx % CH) * 8) : zero8;
+                br[i] = f < F ? *(const f16x8*)(pb_ + row * ldb + (idx % CH) * 8) : zero8;
+            }
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int idx = lane + 64 * i, at = (16 * blk + idx / CH) * PITCH + (idx % CH) * 16;
+                *(f16x8*)(As + at) = ar[i];
+                *(f16x8*)(Bs + at) = br[i];
+            }
+        }
+    };
+    // fragments of a block of 16 frames of two operands: lane (c, g) holds X[16 blk + c][32 h + 8 g .. + 7]
+    auto load_frag = [&](int blk, const f16* pa_, int lda, const f16* pb_, int ldb, f16x8 (&fa)[NS], f16x8 (&fb)[NS]) {
+        const int f = 16 * blk + c;
+        const int64_t row = row_of(f);
+#pragma unroll
+        for (int h = 0; h < NS; ++h) {
+            fa[h] = f < F ? *(const f16x8*)(pa_ + row * lda + g * 8 + 32 * h) : zero8;
+            fb[h] = f < F ? *(const f16x8*)(pb_ + row * ldb + g * 8 + 32 * h) : zero8;
+        }
+    };
+    const f16* const qp = qkv + head * HDIM;
+    const f16* const kp = qp + k_off;
+    const f16* const vp = qp + v_off;
+    const f16* const dop = dout + head * HDIM;
+    const int rr = c * PITCH + 16 * g;                                    // row read: row c, chunk g of a 32-channel step
+    const int tr = (4 * g + (c >> 2)) * PITCH + 8 * (c & 3);              // transposed read: element j = row 4 g + j, column c of a 16-channel block
+
+    // ------------------------------------------------------------------------------------------ sweep 1: dQ, row statistics
+    stage(kp, ld, vp, ld);
+    f16x8 an[NS], bn[NS];
+    load_frag(0, qp, ld, dop, ldo, an, bn);
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                            // this wave's staged rows are in LDS
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int qb = 0; qb < NB; ++qb) {
+        asm volatile("" ::: "memory");                                    // the staged rows are re-read per block: hoisted out of the loop they are 256+ registers
+        f16x8 qf[NS], of[NS];
+#pragma unroll
+        for (int h = 0; h < NS; ++h) { qf[h] = an[h]; of[h] = bn[h]; }
+        if (qb + 1 < NB) load_frag(qb + 1, qp, ld, dop, ldo, an, bn);
+        f32x4 sb[NB], db[NB];                                             // rows k = 16 kb + 4 g + i, column q = 16 qb + c
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb) {
+            sb[kb] = z4;
+            db[kb] = z4;
+#pragma unroll
+            for (int h = 0; h < NS; ++h) {
+                sb[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(As + rr + 16 * kb * PITCH + 64 * h), qf[h], sb[kb], 0, 0, 0);
+                db[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(Bs + rr + 16 * kb * PITCH + 64 * h), of[h], db[kb], 0, 0, 0);
+            }
+        }
+        const bool qlive = 16 * qb + c < F;
+        float m = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { sb[kb][i] = (16 * kb + 4 * g + i < F) ? sb[kb][i] * scale : -INFINITY; m = fmaxf(m, sb[kb][i]); }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        float z = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { sb[kb][i] = (16 * kb + 4 * g + i < F) ? __expf(sb[kb][i] - m) : 0.f; z += sb[kb][i]; }
+        z += __shfl_xor(z, 16);
+        z += __shfl_xor(z, 32);
+        float dd = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { sb[kb][i] = qlive ? sb[kb][i] / z : 0.f; dd += sb[kb][i] * db[kb][i]; }
+        dd += __shfl_xor(dd, 16);
+        dd += __shfl_xor(dd, 32);
+        if (g == 0) { Ms[16 * qb + c] = m; Zs[16 * qb + c] = z; Ds[16 * qb + c] = dd; }
+        f16x4 dsb[NB];                                                    // [kb]: dS^T[k][q], the B operand
+#pragma unroll
+        for (int kb = 0; kb < NB; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dsb[kb][i] = (f16)(sb[kb][i] * (db[kb][i] - dd) * scale);
+        f16* const gq = dqkv + row_of(16 * qb + c) * ldd + head * HDIM + 4 * g;
+#pragma unroll
+        for (int blk = 0; blk < HDIM / 16; ++blk) {
+            f32x4 dq = z4;                                                // dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]
+#pragma unroll
+            for (int kb = 0; kb < NB; ++kb)
+                dq = __builtin_amdgcn_mfma_f32_16x16x16f16(pt_lds_tr16(As + tr + 16 * kb * PITCH + 32 * blk), dsb[kb], dq, 0, 0, 0);
+            if (qlive) *(f16x4*)(gq + 16 * blk) = (f16x4){(f16)dq[0], (f16)dq[1], (f16)dq[2], (f16)dq[3]};
+        }
+    }
+
+    // ------------------------------------------------------------------------------------------ sweep 2: dK, dV
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                            // every read of the K / V rows has returned
+    __builtin_amdgcn_wave_barrier();
+    stage(qp, ld, dop, ldo);
+    load_frag(0, kp, ld, vp, ld, an, bn);
+    __builtin_amdgcn_s_waitcnt(pt_lgkmcnt(0));                            // the Q / dO rows and the row statistics are in LDS
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int kb = 0; kb < NB; ++kb) {
+        asm volatile("" ::: "memory");                                    // as above
+        f16x8 kf[NS], vf[NS];
+#pragma unroll
+        for (int h = 0; h < NS; ++h) { kf[h] = an[h]; vf[h] = bn[h]; }
+        if (kb + 1 < NB) load_frag(kb + 1, kp, ld, vp, ld, an, bn);
+        const bool klive = 16 * kb + c < F;
+        f16x4 pa[NB], dsa[NB];                                            // [qb]: P[q][k], dS[q][k] (rows q = 16 qb + 4 g + i, column k = 16 kb + c)
+#pragma unroll
+        for (int qb = 0; qb < NB; ++qb) {
+            f32x4 sa = z4, da = z4;
+#pragma unroll
+            for (int h = 0; h < NS; ++h) {
+                sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(As + rr + 16 * qb * PITCH + 64 * h), kf[h], sa, 0, 0, 0);
+                da = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(Bs + rr + 16 * qb * PITCH + 64 * h), vf[h], da, 0, 0, 0);
+            }
+            const f32x4 m4 = *(const f32x4*)(Ms + 16 * qb + 4 * g), s4 = *(const f32x4*)(Zs + 16 * qb + 4 * g), d4 = *(const f32x4*)(Ds + 16 * qb + 4 * g);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float p = (klive && 16 * qb + 4 * g + i < F) ? __expf(sa[i] * scale - m4[i]) / s4[i] : 0.f;
+                pa[qb][i] = (f16)p;
+                dsa[qb][i] = (f16)(p * (da[i] - d4[i]) * scale);
+            }
+        }
+        f16* const gk = dqkv + row_of(16 * kb + c) * ldd + head * HDIM + 4 * g;
+#pragma unroll
+        for (int blk = 0; blk < HDIM / 16; ++blk) {
+            f32x4 dv = z4, dk = z4;
+#pragma unroll
+            for (int qb = 0; qb < NB; ++qb) {
+                dv = __builtin_amdgcn_mfma_f32_16x16x16f16(pt_lds_tr16(Bs + tr + 16 * qb * PITCH + 32 * blk), pa[qb], dv, 0, 0, 0);    // dV^T[d][k] = sum_q dO^T[d][q] P[q][k]
+                dk = __builtin_amdgcn_mfma_f32_16x16x16f16(pt_lds_tr16(As + tr + 16 * qb * PITCH + 32 * blk), dsa[qb], dk, 0, 0, 0);   // dK^T[d][k] = sum_q Q^T[d][q] dS[q][k]
+            }
+            if (klive) {
+                *(f16x4*)(gk + k_off + 16 * blk) = (f16x4){(f16)dk[0], (f16)dk[1], (f16)dk[2], (f16)dk[3]};
+                *(f16x4*)(gk + v_off + 16 * blk) = (f16x4){(f16)dv[0], (f16)dv[1], (f16)dv[2], (f16)dv[3]};
+            }
+        }
+    }
+}
+
 template <int D>
 int launch_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldout, const void* dout, int ldo,
                const float* lse, float* dq_dot, void* dq, void* dk, void* dv, int ldd, int nbatch, int S, int heads, float scale, hipStream_t s) {
@@ -639,5 +836,40 @@ extern "C" int pt_attn_temporal_bwd_f16(const void* qkv, int32_t ld, int32_t k_o
     else                { if (F <= 16) PT_TBWD(attn_temporal_bwd_kernel<128>); else PT_TBWD((attn_temporal_bwd2_kernel<128, 2>)); }
 #undef PT_TBWD
     PT_LAUNCH_CHECK("pt_attn_temporal_bwd_f16");
+    return 0;
+}
+
+// ---- include/posetraj_temporal.h: the long-clip extension ----------------------------------------------------------------------------
+extern "C" int ptt_abi_version(void) { return PT_TEMPORAL_ABI_VERSION; }
+
+extern "C" int ptt_attn_temporal_bwd_long_f16(const void* qkv, int32_t ld, int32_t k_off, int32_t v_off, const void* dout, int32_t ldo, void* dqkv,
+                                              int32_t ldd, int32_t B, int32_t F, int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream) {
+    PT_CHECK(qkv && dout && dqkv, "ptt_attn_temporal_bwd_long_f16: null pointer");
+    PT_CHECK(head_dim == 64 || head_dim == 128, "ptt_attn_temporal_bwd_long_f16: head_dim %d unsupported (64, 128)", head_dim);
+    PT_CHECK(F >= 33 && F <= 128, "ptt_attn_temporal_bwd_long_f16: %d frames unsupported (33..128; 1..32: pt_attn_temporal_bwd_f16)", F);
+    PT_CHECK(ld % 8 == 0 && ldo % 8 == 0 && ldd % 4 == 0 && k_off % 8 == 0 && v_off % 8 == 0, "ptt_attn_temporal_bwd_long_f16: pitches / offsets must be multiples of 8 (gradient pitch: 4)");
+    PT_CHECK((((uintptr_t)qkv | (uintptr_t)dout) & 15) == 0 && ((uintptr_t)dqkv & 7) == 0, "ptt_attn_temporal_bwd_long_f16: misaligned pointer");
+    PT_CHECK(B > 0 && S > 0 && heads > 0 && scale > 0.f, "ptt_attn_temporal_bwd_long_f16: bad sizes");
+    const int64_t ntasks = (int64_t)B * S * heads;
+    PT_CHECK(ntasks < (1ll << 31), "ptt_attn_temporal_bwd_long_f16: grid too large");
+    hipStream_t s = (hipStream_t)stream;
+#define PT_TBWD_LONG(NB_, HD_)                                                                                                                \
+    do {                                                                                                                                      \
+        constexpr int W_ = temporal_bwd_long_waves(temporal_bwd_long_slab(NB_, HD_));                                                          \
+        hipLaunchKernelGGL((attn_temporal_bwd_long_kernel<NB_, HD_, W_>), dim3((unsigned)((ntasks + W_ - 1) / W_)), dim3(64 * W_), 0, s,       \
+                           (const f16*)qkv, ld, k_off, v_off, (const f16*)dout, ldo, (f16*)dqkv, ldd, F, S, heads, ntasks, scale);             \
+    } while (0)
+#define PT_TBWD_LONG_HD(NB_) do { if (head_dim == 64) PT_TBWD_LONG(NB_, 64); else PT_TBWD_LONG(NB_, 128); } while (0)
+    switch ((F + 15) / 16) {
+        case 3: PT_TBWD_LONG_HD(3); break;
+        case 4: PT_TBWD_LONG_HD(4); break;
+        case 5: PT_TBWD_LONG_HD(5); break;
+        case 6: PT_TBWD_LONG_HD(6); break;
+        case 7: PT_TBWD_LONG_HD(7); break;
+        default: PT_TBWD_LONG_HD(8); break;
+    }
+#undef PT_TBWD_LONG_HD
+#undef PT_TBWD_LONG
+    PT_LAUNCH_CHECK("ptt_attn_temporal_bwd_long_f16");
     return 0;
 }

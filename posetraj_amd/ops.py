@@ -393,6 +393,8 @@ def attn_q_prescale(head_dim: int) -> float:
 
 
 def attn_temporal(qkv: torch.Tensor, B: int, F: int, S: int, heads: int, head_dim: int) -> torch.Tensor:
+    """Self-attention over the F frames (1 .. 128) of each spatial position, head_dim 64 or 128; token f of (clip b, position s) is row
+    (b F + f) S + s of the fused projection ``qkv`` = [Q | K | V]."""
     _need(qkv, "qkv")
     Cc = heads * head_dim
     out = torch.empty((B * F * S, Cc), dtype=torch.float16, device=qkv.device)

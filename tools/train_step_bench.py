@@ -39,8 +39,9 @@ def main():
     ap.add_argument("--ema", choices=("off", "fused", "separate"), default="off",
                     help="ControlNetTrainer(use_ema=True): the EMA inside the AdamW launch (pt_adamw_ema_f32) or as pt_ema_update_f32 behind pt_adamw_fused_f32")
     ap.add_argument("--temporal-bwd", choices=("fused", "recompute"), default="fused",
-                    help="temporal attention backward of clips of 17 - 32 frames: pt_attn_temporal_bwd_f16 (autodiff.TEMPORAL_FLASH_FRAMES = 32) or the "
-                         "recomputing path through pt_gemm_f16 (16)")
+                    help="temporal attention backward of clips of 17 - 128 frames: the one-launch kernels (17 - 32 frames: pt_attn_temporal_bwd_f16, "
+                         "autodiff.TEMPORAL_FLASH_FRAMES = 32; 33 - 128: ptt_attn_temporal_bwd_long_f16, autodiff.TEMPORAL_LONG_BACKWARD) or the "
+                         "recomputing path through pt_gemm_f16 (TEMPORAL_FLASH_FRAMES = 16, TEMPORAL_LONG_BACKWARD off)")
     ap.add_argument("--optimizer", choices=("adamw", "adamw8bit"), default="adamw",
                     help="adamw8bit: ControlNetTrainer(use_8bit_adam=True), block-quantised moments updated by pto_adamw8_f32")
     ap.add_argument("--gradient-checkpointing", choices=("off", "controlnet", "all"), default="off",
@@ -57,6 +58,7 @@ def main():
     from posetraj_amd import autodiff
     from posetraj_amd.training import ControlNetTrainer
     autodiff.TEMPORAL_FLASH_FRAMES = 32 if a.temporal_bwd == "fused" else 16
+    autodiff.TEMPORAL_LONG_BACKWARD = a.temporal_bwd == "fused"
     dev = torch.device("cuda:0")
     if a.optimizer_launch:
         return optimizer_launch(a.optimizer_launch, a.tiny, dev)
