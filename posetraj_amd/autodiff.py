@@ -565,6 +565,8 @@ def dense(tape: Tape, x: Var, L: Dense, *, geom=None, res: Optional[Var] = None,
     """``y = L(x [| x1]) (+ res)``.  ``geom = (Nimg, H, W)`` of the input for convolutions (``(B, F, S)`` for the temporal ones)."""
     if x1 is not None and L.P.trainable:
         raise RuntimeError("weight gradients of a two-source layer are not implemented (only the frozen U-Net's up blocks have them)")
+    if upsample2x and L.P.trainable:                           # accumulate() would pair dy's 4 x rows with the un-upsampled x and geom
+        raise RuntimeError("the weight gradient of an upsampling layer is not implemented (only the frozen U-Net's upsamplers have one)")
     fwd, _ = L.packs()
     if geom is None and x1 is None and _few_rows(x.v, fwd):
         y = gemv(x.v, fwd, None if res is None else res.v)
