@@ -734,6 +734,35 @@ def add_rowvec(tape: Tape, x: Var, vec: Var, rows_per_vec: int) -> Var:
     return out
 
 
+def add_rowvec_interleaved(tape: Tape, x: Var, vec: Var, B: int, F: int, S: int) -> Var:
+    """``y[r] = x[r] + vec[j(r)]``, ``j(r) = (b S + s) mod B`` for row ``r = (b F + f) S + s``: the TEMPORAL blocks' collapsed
+    cross-attention of a batch of ``B`` clips, whose context the reference builds ``[H W, B]``-major against ``[B, H W]``-major tokens
+    (``blocks.py``: ``vec_mode=2``).  ``ptb_add_rowvec_interleaved_f16`` / ``ptb_colsum_interleaved_f16``
+    (include/posetraj_batch.h); under ``DETERMINISTIC`` the two-launch reduction through a workspace of its own."""
+    rows, Cc = x.v.shape
+    if rows != B * F * S or tuple(vec.v.shape) != (B, Cc):
+        raise ValueError(f"add_rowvec_interleaved: x {tuple(x.v.shape)} / vec {tuple(vec.v.shape)} against (B, F, S) = ({B}, {F}, {S})")
+    y = torch.empty_like(x.v)
+    hip.checked().ptb_add_rowvec_interleaved_f16(x.v.data_ptr(), vec.v.data_ptr(), B, F, S, Cc, y.data_ptr(), _stream())
+    out = Var(y)
+
+    def bwd(dy):
+        _acc(x, dy)
+        if vec.need:
+            L = hip.checked()
+            d = dy.contiguous()
+            s = torch.zeros((B, Cc), dtype=torch.float32, device=dy.device)
+            if DETERMINISTIC:
+                ws = _ws(L.ptb_colsum_interleaved_ws_floats(B, F, S, Cc), dy.device)
+                L.ptb_colsum_interleaved_det_f16(d.data_ptr(), B, F, S, Cc, s.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            else:
+                L.ptb_colsum_interleaved_f16(d.data_ptr(), B, F, S, Cc, s.data_ptr(), _stream())
+            _acc(vec, s.to(torch.float16))
+
+    tape.op(out, bwd)
+    return out
+
+
 def blend(tape: Tape, a: Var, b: Var, M: Mix) -> Var:
     """AlphaBlender (``merge_strategy="learned_with_images"`` with an all-zero indicator): ``alpha a + (1 - alpha) b``."""
     L, ap = hip.checked(), M.ptr()
@@ -804,6 +833,36 @@ def rows(tape: Tape, x: Var, r0: int, r1: int, defer: Optional[list] = None) -> 
             add_rows(x, r0, r1, dy)
         elif x.need:
             defer.append((x, r0, r1, dy))
+
+    tape.op(out, bwd)
+    return out
+
+
+def repeat_rows(tape: Tape, x: Var, B: int) -> Var:
+    """``x`` ``[n, C]`` tiled ``B`` times along the rows (the frame position embedding, the same for every clip of a batch); the
+    gradient is the sum over the copies (``pt_colsum_f16`` over ``B`` rows of ``n C`` columns)."""
+    n, Cc = x.v.shape
+    out = Var(x.v.repeat(B, 1))
+
+    def bwd(dy):
+        s = torch.zeros((1, n * Cc), dtype=torch.float32, device=dy.device)
+        colsum(dy.contiguous().view(B, n * Cc), B, 1, s)
+        _acc(x, s.to(torch.float16).view(n, Cc))
+
+    tape.op(out, bwd)
+    return out
+
+
+def concat_rows(tape: Tape, parts: List[Var]) -> Var:
+    """``cat(parts)`` along the rows (one frame of every clip of a batch, gathered for the spatial-loss pass): a copy forward, row
+    slices of the gradient back."""
+    out = Var(torch.cat([p.v for p in parts], dim=0))
+
+    def bwd(dy):
+        r = 0
+        for p in parts:
+            _acc(p, dy[r:r + p.v.shape[0]])
+            r += p.v.shape[0]
 
     tape.op(out, bwd)
     return out

@@ -13,7 +13,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.abspath(os.environ["PT_LIB"]) if os.environ.get("PT_LIB") else os.path.join(HERE, "libposetraj_hip.so")   # PT_LIB: A/B against another build on one box
-SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip"]
+SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip", "batch.hip"]
 HEADERS = ["pt_common.h", "igemm_tail.h", "pt_fold.h"]
 HEADER = os.path.join(HERE, "..", "include", "posetraj_hip.h")
 STRUCT_CLASSES = {"pt_igemm_params": "IgemmParams", "pt_ffn_params": "FfnParams", "pt_lnlin_params": "LnLinParams",
@@ -25,6 +25,8 @@ OPTIM_STRUCT_CLASSES = {"pt_adam8_segment": "Adam8Segment"}
 DET_HEADER = os.path.join(HERE, "..", "include", "posetraj_det.h")
 # the long-clip extension (include/posetraj_temporal.h: entry points `ptt_*`, a version of its own): temporal attention backward of 33 - 128 frames
 TEMPORAL_HEADER = os.path.join(HERE, "..", "include", "posetraj_temporal.h")
+# the clip-batch extension (include/posetraj_batch.h: entry points `ptb_*`, a version of its own): the temporal blocks' cross-attention rows of a batch
+BATCH_HEADER = os.path.join(HERE, "..", "include", "posetraj_batch.h")
 
 _lib = _checked = None
 
@@ -35,7 +37,7 @@ _lib = _checked = None
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _TYPE = r"(?:const\s+)?\w+\s*\*?"
 _DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
-                            | (?P<ret>%s)\s*\b(?P<fn>pt[odt]?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
+                            | (?P<ret>%s)\s*\b(?P<fn>pt[odtb]?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
                             | extern\s+"C"\s*\{ | \} )""" % _TYPE, re.X)
 _FIELD = re.compile(r"(%s)\s*\b(\w+(?:\s*,\s*\w+)*)" % _TYPE)         # `int32_t C0, C1`, `const void* x0`; a parameter is the one-name case
 
@@ -91,7 +93,7 @@ def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macr
             params = m.group("params").strip()
             protos[m.group("fn")] = (" ".join(m.group("ret").split()), [] if params == "void" else [t for t, _ in _declarators(params, ",")])
         pos = m.end()
-    named = re.findall(r"pt[odt]?_[a-z0-9_]+\s*\(", text)
+    named = re.findall(r"pt[odtb]?_[a-z0-9_]+\s*\(", text)
     if len(named) != len(protos):
         raise ValueError(f"posetraj_hip.h: {len(named)} names are followed by '(' but {len(protos)} prototypes were read")
     return int(version.group(1)), {k: v for k, v in structs.items() if k not in (known_structs or {})}, protos
@@ -113,6 +115,9 @@ DET_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUC
 with open(TEMPORAL_HEADER) as _f:
     TEMPORAL_ABI_VERSION, _, TEMPORAL_PROTOTYPES = _parse_header(_f.read(), {}, "PT_TEMPORAL_ABI_VERSION", _STRUCTS)
 TEMPORAL_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in TEMPORAL_PROTOTYPES.items()}
+with open(BATCH_HEADER) as _f:
+    BATCH_ABI_VERSION, _, BATCH_PROTOTYPES = _parse_header(_f.read(), {}, "PT_BATCH_ABI_VERSION", _STRUCTS)
+BATCH_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in BATCH_PROTOTYPES.items()}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -123,7 +128,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -200,7 +205,7 @@ def source_digest() -> str:
     to replay them for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER]):
+    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER]):
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
     return h.hexdigest()
@@ -215,17 +220,17 @@ def _load(errcheck=None):
                            "(posetraj_amd has no CPU or PyTorch fallback path)")
     L = C.CDLL(LIB_PATH)
     for sigs, protos in ((SIGNATURES, PROTOTYPES), (OPTIM_SIGNATURES, OPTIM_PROTOTYPES), (DET_SIGNATURES, DET_PROTOTYPES),
-                         (TEMPORAL_SIGNATURES, TEMPORAL_PROTOTYPES)):
+                         (TEMPORAL_SIGNATURES, TEMPORAL_PROTOTYPES), (BATCH_SIGNATURES, BATCH_PROTOTYPES)):
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)            # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
-            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version", "ptd_abi_version", "ptt_abi_version"):
+            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version", "ptd_abi_version", "ptt_abi_version", "ptb_abi_version"):
                 fn.errcheck = errcheck
     if (L.pt_abi_version() != ABI_VERSION or L.pto_abi_version() != OPTIM_ABI_VERSION or L.ptd_abi_version() != DET_ABI_VERSION
-            or L.ptt_abi_version() != TEMPORAL_ABI_VERSION):
+            or L.ptt_abi_version() != TEMPORAL_ABI_VERSION or L.ptb_abi_version() != BATCH_ABI_VERSION):
         raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} / optimizer extension {L.pto_abi_version()} / deterministic extension "
-                           f"{L.ptd_abi_version()} / long-clip extension {L.ptt_abi_version()} != expected {ABI_VERSION} / {OPTIM_ABI_VERSION} / "
-                           f"{DET_ABI_VERSION} / {TEMPORAL_ABI_VERSION}; rebuild")
+                           f"{L.ptd_abi_version()} / long-clip extension {L.ptt_abi_version()} / clip-batch extension {L.ptb_abi_version()} != expected "
+                           f"{ABI_VERSION} / {OPTIM_ABI_VERSION} / {DET_ABI_VERSION} / {TEMPORAL_ABI_VERSION} / {BATCH_ABI_VERSION}; rebuild")
     return L
 
 

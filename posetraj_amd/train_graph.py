@@ -23,10 +23,10 @@ from .modeling import _tup
 
 
 class TrainCtx:
-    """Per-forward state: one clip (B = 1; the reference's spatial loss indexes by frame, ``:1396-1402``)."""
+    """Per-forward state: ``B`` clips of ``F`` frames; ``emb_silu`` ``[B, 4 ch0]`` and ``ehs`` ``[B, D]`` hold one row per clip."""
 
-    def __init__(self, F: int, emb_silu: Var, ehs: Var):
-        self.B, self.F, self.emb_silu, self.ehs = 1, F, emb_silu, ehs
+    def __init__(self, F: int, emb_silu: Var, ehs: Var, B: int = 1):
+        self.B, self.F, self.emb_silu, self.ehs = B, F, emb_silu, ehs
 
 
 class ResBlock:
@@ -96,6 +96,8 @@ class Transformer:
         h = AD.dense(tape, AD.groupnorm(tape, x, self.norm, rows_per_sample=S, n_samples=N, eps=1e-6, silu=False), self.proj_in)
         t = Var(ops.timestep_embedding(torch.arange(F, dtype=torch.float32, device=x.v.device), C), need=False)
         emb = AD.dense(tape, AD.silu(tape, AD.dense(tape, t, self.tpe1)), self.tpe2)                      # [F, C]
+        if B > 1:
+            emb = AD.repeat_rows(tape, emb, B)                                                            # [B F, C]: every clip counts its frames from 0
         ff = lambda y, w1, w2, res: AD.dense(tape, AD.geglu(tape, AD.dense(tape, y, w1)), w2, res=res)
         for L in self.layers:
             a = AD.attn_spatial(tape, AD.dense(tape, AD.layernorm(tape, h, L.ln1), L.qkv), N, S, heads, hd)
@@ -106,7 +108,9 @@ class Transformer:
             u = ff(AD.layernorm(tape, u, L.ln_in), L.fi1, L.fi2, u)
             a = AD.attn_temporal(tape, AD.dense(tape, AD.layernorm(tape, u, L.tln1), L.tqkv), B, F, S, heads, hd)
             u = AD.dense(tape, a, L.to, res=u)
-            u = AD.add_rowvec(tape, u, AD.dense(tape, AD.dense(tape, ctx.ehs, L.txv), L.txo), F * S)
+            xa = AD.dense(tape, AD.dense(tape, ctx.ehs, L.txv), L.txo)
+            # a batch's temporal context is built [H W, B]-major against [B, H W]-major tokens: row (b F + f) S + s gets clip (b S + s) mod B
+            u = AD.add_rowvec(tape, u, xa, F * S) if B == 1 else AD.add_rowvec_interleaved(tape, u, xa, B, F, S)
             u = ff(AD.layernorm(tape, u, L.tln3), L.tf1, L.tf2, u)
             h = AD.blend(tape, hs, u, self.mix)
         return AD.dense(tape, h, self.proj_out, res=x)
@@ -136,11 +140,13 @@ class TimeEmbedding:
         self.t1, self.t2, self.a1, self.a2 = lin("time_embedding.linear_1"), lin("time_embedding.linear_2"), lin("add_embedding.linear_1"), lin("add_embedding.linear_2")
 
     def run(self, tape, timestep: torch.Tensor, added_time_ids: torch.Tensor, device) -> Var:
-        t = timestep.to(device=device, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        ids = added_time_ids.to(device=device, dtype=torch.float32)
+        B = ids.shape[0] if ids.dim() > 1 else 1                  # one row [fps, noise_aug, motion_bucket] per clip
+        t = timestep.to(device=device, dtype=torch.float32).reshape(-1)
+        t = (t[:1] if B == 1 else t.expand(B)).contiguous()
         te = Var(ops.timestep_embedding(t, self.ch0), need=False)
         emb = AD.dense(tape, AD.silu(tape, AD.dense(tape, te, self.t1)), self.t2)
-        ids = added_time_ids.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-        ae = Var(ops.timestep_embedding(ids, self.add_dim).view(1, -1), need=False)
+        ae = Var(ops.timestep_embedding(ids.reshape(-1).contiguous(), self.add_dim).view(B, -1), need=False)
         emb = AD.dense(tape, AD.silu(tape, AD.dense(tape, ae, self.a1)), self.a2, res=emb)
         return AD.silu(tape, emb)
 
@@ -182,12 +188,16 @@ class ControlNetGraph:
 
     def run(self, tape: Tape, sample_cl: torch.Tensor, geom, timestep, ehs: torch.Tensor, added_time_ids, cond: torch.Tensor,
             conditioning_scale: float = 1.0, camera_cond: Optional[torch.Tensor] = None, checkpoint: bool = False):
-        """``sample_cl``: the network input channels-last ``[F h w, 8]``; ``cond``: ``[F, 3, H, W]`` trajectory maps; ``camera_cond``:
-        ``[F, 12]`` (R|T per frame) for the camera twin.  ``checkpoint``: every residual block and every transformer is a
-        checkpointed segment (``controlnet.enable_gradient_checkpointing()``)."""
+        """``sample_cl``: the network input channels-last ``[B F h w, 8]``, ``geom`` = ``(B F, h, w)``; ``ehs``: ``[B, D]``; ``cond``:
+        ``[B F, 3, H, W]`` trajectory maps; ``camera_cond``: ``[B F, 12]`` (R|T per frame) for the camera twin.  ``B`` is the number of
+        rows of ``ehs``.  ``checkpoint``: every residual block and every transformer is a checkpointed segment
+        (``controlnet.enable_gradient_checkpointing()``)."""
         N, h, w = geom
         dev = sample_cl.device
-        ctx = TrainCtx(N, self.time.run(tape, timestep, added_time_ids, dev), Var(ehs, need=False))
+        B = ehs.shape[0]
+        if N % B:
+            raise ValueError(f"ControlNetGraph.run: {N} frames do not divide into {B} clips")
+        ctx = TrainCtx(N // B, self.time.run(tape, timestep, added_time_ids, dev), Var(ehs, need=False), B)
         Fc, Cc, H, W = cond.shape
         c = Var(ops.to_channels_last(cond, cpad=8).view(Fc * H * W, 8), need=False)
         c = AD.silu(tape, AD.dense(tape, c, self.ce_in, geom=(Fc, H, W)))
@@ -251,7 +261,7 @@ class UNetDecoderGraph:
         """``state``: what ``UNetSpatioTemporalConditionControlNetModel._encode`` returned (inference kernels).  ``checkpoint``: every
         residual block (two-source: it closes over its skip) and every transformer is a checkpointed segment."""
         Bc, F = state["dims"]
-        ctx = TrainCtx(F, Var(emb_silu, need=False), Var(ehs, need=False))
+        ctx = TrainCtx(F, Var(emb_silu, need=False), Var(ehs, need=False), Bc)
         skips = []
         for s, r, m in zip(state["skips"], residuals, mult):
             n, hh, ww, c = s.shape

@@ -96,16 +96,42 @@ def _edm_loss(pred: torch.Tensor, noisy: torch.Tensor, target: torch.Tensor, sig
     return out
 
 
+def _check_batch(B, F, *, encoder_hidden_states, motion_values, trajectories, noise, sigmas, random_p, camera_cond, noise_shape) -> None:
+    """The per-clip arguments of a step against the batch size of ``latents``: ``ValueError`` naming the argument."""
+    def lead(name, t, want):
+        if t is not None and (t.dim() < len(want) or tuple(t.shape[:len(want)]) != want):
+            raise ValueError(f"{name} must lead with {list(want)} (latents hold {B} clip(s) of {F} frames); got {tuple(t.shape)}")
+
+    def count(name, t):
+        n = None if t is None else (t.numel() if torch.is_tensor(t) else len(t) if hasattr(t, "__len__") else 1)
+        if n is not None and n != B:
+            raise ValueError(f"{name} must hold one value per clip ({B}); got {n}")
+
+    lead("encoder_hidden_states", encoder_hidden_states, (B,))
+    lead("trajectories", trajectories, (B, F))
+    count("motion_values", motion_values)
+    count("sigmas", sigmas)
+    count("random_p", random_p)
+    if noise is not None and tuple(noise.shape) != noise_shape:
+        raise ValueError(f"noise must have the shape of latents {noise_shape}; got {tuple(noise.shape)}")
+    if camera_cond is not None:
+        cam = torch.as_tensor(camera_cond)
+        if cam.dim() != 3 or tuple(cam.shape) != (B, F, 12):
+            raise ValueError(f"camera_cond must be [{B}, {F}, 12] (R|T per frame of every clip); got {tuple(cam.shape)}")
+
+
 def _step_inputs(dev, latents, encoder_hidden_states, motion_values, trajectories, unet, *, scaling_factor, conditioning_dropout_prob, use_spatial,
-                 noise, sigmas, random_p, ran_idx, generator, kernel: bool = True, lazy_traj: bool = False):
+                 noise, sigmas, random_p, ran_idx, generator, kernel: bool = True, lazy_traj: bool = False, camera_cond=None):
     """``:1275-1345``: the step's random draws (sampled here when not given), noising, EDM preconditioning, conditioning dropout,
-    ``added_time_ids``.  Returns a dict of device tensors; ``x`` is the network input channels-last ``[B, F, h, w, 8]``."""
+    ``added_time_ids``.  Returns a dict of device tensors; ``x`` is the network input channels-last ``[B, F, h, w, 8]``.  Every per-clip
+    argument must lead with the batch size of ``latents`` (``ValueError`` naming the argument); ``ran_idx`` is one frame index per step.
+    ``camera_cond`` ``[B, F, 12]`` is only checked and passed on (``cam``, fp32 on the host)."""
+    if latents.dim() != 5 or latents.shape[2] != 4:
+        raise ValueError(f"latents must be [batch, frames, 4, h, w]; got {tuple(latents.shape)}")
     lat = latents.to(device=dev, dtype=torch.float32).contiguous()
     B, F, Cz, h, w = lat.shape
-    if Cz != 4:
-        raise ValueError(f"latents must be [batch, frames, 4, h, w]; got {tuple(latents.shape)}")
-    if use_spatial and B != 1:
-        raise ValueError("the spatial loss indexes the ControlNet residuals by frame (`sample[ran_idx]`, :1396-1398): batch size 1 only")
+    _check_batch(B, F, encoder_hidden_states=encoder_hidden_states, motion_values=motion_values, trajectories=trajectories, noise=noise,
+                 sigmas=sigmas, random_p=random_p, camera_cond=camera_cond, noise_shape=tuple(lat.shape))
     if noise is None:
         noise = torch.randn(lat.shape, generator=generator, dtype=torch.float32)                 # torch.randn_like(latents)
     if sigmas is None:
@@ -128,6 +154,8 @@ def _step_inputs(dev, latents, encoder_hidden_states, motion_values, trajectorie
     ids = train_add_time_ids(6, motion_values, TRAIN_NOISE_AUG, torch.float32, B, unet, device=dev)
     I = dict(lat=lat, noise=noise, sig=sig, cond_scale=cond_scale, sig_host=sig_host, timesteps=timesteps, ids=ids, ehs=ehs,
              ran_idx=ran_idx, dims=(B, F, h, w))
+    if camera_cond is not None:
+        I["cam_host"] = torch.as_tensor(camera_cond, dtype=torch.float32)
     if lazy_traj:                                             # the largest input (15 MB at 320 x 576; a host-side cast + copy of ~6 ms): the trainer
         I["traj_src"] = trajectories                          # stages it AFTER it has launched the frozen encoder, which does not read it
     else:
@@ -158,8 +186,11 @@ def controlnet_training_loss(controlnet, unet, latents: torch.Tensor, encoder_hi
     latents x scaling_factor), ``encoder_hidden_states`` ``[B, 1, D]`` (CLIP embedding of the first frame), ``motion_values``
     ``[B]``, ``trajectories`` ``[B, F, 3, H, W]`` in [-1, 1].  ``noise`` / ``sigmas`` / ``random_p`` / ``ran_idx``: the step's random
     draws, sampled here (``generator``) when not given.  Returns ``loss`` (= temporal + 0.5 spatial), ``loss_temporal``,
-    ``loss_spatial`` as floats and the intermediate tensors.  ``use_spatial`` follows the reference's hard-wired ``True`` and, like
-    its ``sample[ran_idx]`` indexing, needs a batch of one clip.  For the step WITH its backward see ``ControlNetTrainer``."""
+    ``loss_spatial`` as floats and the intermediate tensors; the losses are means over the clips.  ``use_spatial`` follows the
+    reference's hard-wired ``True``.  For a batch the spatial loss is taken PER CLIP - clip b's own residual rows of frame ``ran_idx``, its
+    own sigma, noisy latent and target, then the mean over the clips - where the reference's expression, written for one clip, takes
+    clip 0's residuals for every clip and a B x B cross product of predictions and sigmas; one clip: the same
+    computation.  For the step WITH its backward see ``ControlNetTrainer``."""
     dev = unet.device
     if dev is None:
         raise RuntimeError("controlnet_training_loss: the U-Net has no weights loaded")
@@ -176,9 +207,11 @@ def controlnet_training_loss(controlnet, unet, latents: torch.Tensor, encoder_hi
     out = dict(loss=loss_t, loss_temporal=loss_t, loss_spatial=None, model_pred=pred, inp_noisy_latents=inp, timesteps=timesteps,
                added_time_ids=ids, encoder_hidden_states=ehs, noise=I["noise"], sigmas=I["sig_host"], ran_idx=ran_idx)
     if use_spatial:                                                                              # :1388-1407
+        B, F = I["dims"][:2]
+        frame = (lambda d: d[ran_idx].unsqueeze(0)) if B == 1 else (lambda d: d[ran_idx::F])    # frame ran_idx of every clip: rows b F + ran_idx
         pred_s = unet(inp[:, ran_idx].unsqueeze(1), timesteps, ehs, added_time_ids=ids,
-                      down_block_additional_residuals=[d[ran_idx].unsqueeze(0) for d in down],
-                      mid_block_additional_residual=mid[ran_idx].unsqueeze(0), return_dict=False)[0]
+                      down_block_additional_residuals=[frame(d) for d in down],
+                      mid_block_additional_residual=frame(mid), return_dict=False)[0]
         ls = _edm_loss(pred_s, noisy[:, ran_idx:ran_idx + 1].contiguous(), lat[:, ran_idx:ran_idx + 1].contiguous(), sig)
         out["loss_spatial"] = float(ls.mean())
         out["loss"] = loss_t + 0.5 * out["loss_spatial"]
@@ -256,6 +289,19 @@ class ControlNetTrainer:
     no waiting between workgroups.  The forward and the attention backward were bit-reproducible already.  Under ``torch.distributed``
     the flag is accepted, but nothing is claimed across ranks: the all-reduce's order is the collective library's.  Nor across library
     builds or tile-plan changes.  A checkpoint file knows nothing of the mode.  Not with ``use_graph``.  Cost: DESIGN 4.13.
+
+    Batches of clips (``--per_gpu_batch_size``): ``loss_and_grads`` / ``step`` take ``B`` clips at once - ``latents [B, F, 4, h, w]``,
+    ``encoder_hidden_states [B, 1, D]``, ``motion_values [B]``, ``trajectories [B, F, 3, H, W]``, ``camera_cond [B, F, 12]``, ``noise``,
+    ``sigmas [B]``, ``random_p [B]`` and ONE ``ran_idx`` - in one pass of the tape over ``B F`` frames; a mismatched batch dimension is a
+    ``ValueError`` naming the argument.  The losses are the means over the clips (``:1381-1386``), so each clip's gradient carries 1 / B;
+    under accumulation and data parallel a batch counts like one micro-batch (each rank's gradient is that of its local batch mean).
+    As in the reference, the clips of a batch are not independent: the temporal blocks' cross-attention hands token ``(b, f, s)`` the
+    context of clip ``(b S + s) mod B`` (``autodiff.add_rowvec_interleaved``, include/posetraj_batch.h), so a batch of two is
+    not two accumulated micro-batches.  The spatial loss is taken PER CLIP - clip b's own residual rows of frame ``ran_idx``, its own
+    sigma, noisy latent and target, the mean over clips - where the reference's expression, written for one clip, broadcasts clip 0's
+    residuals and crosses every prediction with every sigma.  ``B == 1`` issues the launches it always did.  Every
+    mode above works on a batch without code of its own, ``deterministic`` included (the new reduction has its two-launch form);
+    ``use_graph=True`` refuses a batch with a ``ValueError``.  What a batch buys at 14 x 320 x 576: DESIGN 4.13.
 
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
@@ -341,24 +387,29 @@ class ControlNetTrainer:
     #    loss_scale x the gradient of the mean micro-batch loss
     def loss_and_grads(self, latents, encoder_hidden_states, motion_values, trajectories, *, use_spatial: bool = True, noise=None,
                        sigmas=None, random_p=None, ran_idx=None, generator=None, camera_cond=None) -> dict:
-        """``camera_cond`` ``[1, F, 12]``: the camera twin's per-frame R|T (``scripts/train_svd_traj_VIPSeg_14_cam_concat.py:1393,1409``;
-        that script has no spatial loss: ``use_spatial=False``)."""
+        """A micro-batch of ``B`` clips (``--per_gpu_batch_size``): ``latents`` ``[B, F, 4, h, w]``, ``encoder_hidden_states``
+        ``[B, 1, D]``, ``motion_values`` ``[B]``, ``trajectories`` ``[B, F, 3, H, W]``, ``noise`` like ``latents``, ``sigmas`` / ``random_p``
+        ``[B]``, ONE ``ran_idx`` (the reference draws one per step); a mismatched batch dimension is a ``ValueError`` naming the argument.
+        The losses are the means over the clips, so every clip's gradient carries 1 / B.  ``camera_cond`` ``[B, F, 12]``: the camera twin's
+        per-frame R|T (``scripts/train_svd_traj_VIPSeg_14_cam_concat.py:1393,1409``; that script has no spatial loss:
+        ``use_spatial=False``)."""
         unet, dev = self.unet, self.device
         t_host = time.perf_counter()
+        if camera_cond is not None and not self.config.get("camera"):
+            raise ValueError("camera_cond given to a ControlNet without the camera branch (config camera=False)")
         I = _step_inputs(dev, latents, encoder_hidden_states, motion_values, trajectories, unet, scaling_factor=self.scaling_factor,
                          conditioning_dropout_prob=self.dropout, use_spatial=use_spatial, noise=noise, sigmas=sigmas, random_p=random_p,
-                         ran_idx=ran_idx, generator=generator, kernel=False, lazy_traj=True)
+                         ran_idx=ran_idx, generator=generator, kernel=False, lazy_traj=True, camera_cond=camera_cond)
         B, F, h, w = I["dims"]
-        if B != 1:
-            raise ValueError("ControlNetTrainer takes one clip per step (the reference trains with --per_gpu_batch_size=1)")
+        if B != 1 and self.use_graph:
+            raise ValueError("ControlNetTrainer(use_graph=True) takes one clip per step: the captured step has not been verified for a batch "
+                             f"(got {B} clips); build the trainer with use_graph=False for per_gpu_batch_size > 1")
         if self._accum_scale is None:                    # the loss scale of this accumulation cycle (it only changes between cycles)
             self._accum_scale = self.loss_scale
         scale = self._accum_scale / self.accumulation    # accelerate divides each micro-batch's loss by the number of micro-batches
-        cam = None
-        if camera_cond is not None:
-            if not self.config.get("camera"):
-                raise ValueError("camera_cond given to a ControlNet without the camera branch (config camera=False)")
-            cam = torch.as_tensor(camera_cond, dtype=torch.float32)[0]
+        cam = I.pop("cam_host", None)
+        if cam is not None:
+            cam = cam.reshape(B * F, 12)
         ran_idx = I["ran_idx"]
         I["timesteps"] = I["timesteps"].to(device=dev, dtype=torch.float32)
         I["ehs"] = I["ehs"].to(device=dev, dtype=torch.float32)
@@ -376,11 +427,11 @@ class ControlNetTrainer:
         self._micro += 1
         self._packs_built = self._packs_built or bool(use_spatial)
         t_host = time.perf_counter() - t_host                 # everything is enqueued; reading the loss is the first wait for the device
-        loss_t = float(lt)
+        loss_t = float(lt) if B == 1 else float(lt.mean())    # (per-clip means, then the mean over the clips: :1381-1386)
         out = dict(loss=loss_t, loss_temporal=loss_t, loss_spatial=None, grad_scale=scale, ran_idx=ran_idx, sigmas=I["sig_host"],
                    host_enqueue_ms=1000.0 * t_host, graph_replay=bool(graphed))
         if ls is not None:
-            out["loss_spatial"] = float(ls)
+            out["loss_spatial"] = float(ls) if B == 1 else float(ls.mean())
             out["loss"] = loss_t + 0.5 * out["loss_spatial"]
         return out
 
@@ -438,7 +489,7 @@ class ControlNetTrainer:
             self.params.refresh_alphas()
         _edm_train_input(I)
         lat, noisy, sig, timesteps, ids = I["lat"], I["noisy"], I["sig"], I["timesteps"], I["ids"]
-        ehs16 = I["ehs"].to(dtype=torch.float16).reshape(1, -1).contiguous()
+        ehs16 = I["ehs"].to(dtype=torch.float16).reshape(B, -1).contiguous()
         inp = I["x"].permute(0, 1, 4, 2, 3)
         L = hip.checked()
         # three tapes: the ControlNet's forward, the decoder pass of the temporal loss and the one-frame decoder pass of the spatial
@@ -463,17 +514,18 @@ class ControlNetTrainer:
         if self._packs_pending:                               # the packs re-written behind the last optimizer step (their own stream)
             main.wait_stream(self._pk_stream)
             self._packs_pending = False
-        outs, mid = self.controlnet.run(tape_cn, I["x"].view(F * h * w, 8), (F, h, w), timesteps, ehs16, ids, I["traj"][0], camera_cond=cam,
+        traj = I["traj"][0] if B == 1 else I["traj"].reshape((B * F,) + tuple(I["traj"].shape[2:]))
+        outs, mid = self.controlnet.run(tape_cn, I["x"].view(B * F * h * w, 8), (B * F, h, w), timesteps, ehs16, ids, traj, camera_cond=cam,
                                         checkpoint=self._ckpt_cn)
         with torch.no_grad():
-            emb_silu = unet.time.run(timesteps, ids, 1)
+            emb_silu = unet.time.run(timesteps, ids, B)
 
-        def loss_of(p: AD.Var, nz, tg, frames, weight):
-            out = torch.empty(1, dtype=torch.float32, device=dev)
-            L.pt_edm_loss(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
+        def loss_of(p: AD.Var, nz, tg, frames, weight):      # per-clip losses [B]; the gradient is that of their mean (the kernel divides by B)
+            out = torch.empty(B, dtype=torch.float32, device=dev)
+            L.pt_edm_loss(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), B, frames, h * w,
                           out.data_ptr(), ops._stream())
             g = torch.empty((p.v.shape[0], 8), dtype=torch.float16, device=dev)
-            L.pt_edm_loss_bwd(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), 1, frames, h * w,
+            L.pt_edm_loss_bwd(p.v.data_ptr(), 0, p.v.shape[-1], nz.data_ptr(), tg.data_ptr(), sig.data_ptr(), B, frames, h * w,
                               float(scale * weight), g.data_ptr(), ops._stream())
             p.g = g
             return out
@@ -493,8 +545,13 @@ class ControlNetTrainer:
                 with torch.no_grad():
                     state_s = unet._encode(inp[:, ran_idx].unsqueeze(1), timesteps, I["ehs"], ids)
                 mult_s = unet._multiplicity(state_s, len(outs))
-                res_s = [AD.rows(tape_sp, o, ran_idx * (o.v.shape[0] // F), (ran_idx + 1) * (o.v.shape[0] // F), defer=deferred) for o in outs]
-                mid_s = AD.rows(tape_sp, mid, ran_idx * (mid.v.shape[0] // F), (ran_idx + 1) * (mid.v.shape[0] // F), defer=deferred)
+                def frame(o):                                # clip b's own rows of frame ran_idx, b = 0 .. B - 1 (a batch of B one-frame clips)
+                    n = o.v.shape[0] // (B * F)
+                    parts = [AD.rows(tape_sp, o, (b * F + ran_idx) * n, (b * F + ran_idx + 1) * n, defer=deferred) for b in range(B)]
+                    return parts[0] if B == 1 else AD.concat_rows(tape_sp, parts)
+
+                res_s = [frame(o) for o in outs]
+                mid_s = frame(mid)
                 pred_s = self.decoder.run(tape_sp, state_s, mult_s, res_s, mid_s, emb_silu, ehs16, checkpoint=self._ckpt_dec)
                 ls = loss_of(pred_s, noisy[:, ran_idx:ran_idx + 1].contiguous(), lat[:, ran_idx:ran_idx + 1].contiguous(), 1, 0.5)
         if state is None:

@@ -4,10 +4,11 @@ random init, synthetic latents / trajectory maps.  Prints ms per step (forward +
 of the three families (pt_igemm_f16: forward and data gradients; pt_gemm_f16: weight gradients and attention backward) and
 the memory high-water mark.
 
-    python tools/train_step_bench.py [--steps 5] [--height 320 --width 576] [--frames 14] [--tiny] [--gemm-table] [--igemm-table]
+    python tools/train_step_bench.py [--steps 5] [--height 320 --width 576] [--frames 14] [--batch 1] [--tiny] [--gemm-table] [--igemm-table]
         [--temporal-bwd fused|recompute] [--optimizer adamw|adamw8bit] [--gradient-checkpointing off|controlnet|all] [--deterministic]
     python tools/train_step_bench.py --optimizer-launch 3          # the optimizer's launch alone at the full parameter count: pt_adamw_fused_f32
         against pto_adamw8_f32 (and their EMA forms), that many interleaved rounds
+    python tools/train_step_bench.py --batch-kernels 2             # the two kernels of include/posetraj_batch.h alone at the level-0 shape of that many clips
     python tools/train_step_bench.py --json --steps 7 --warmup 3      # what bench.py --train-step runs as a child process:
         wall-clock median without hipEvent brackets, the host's enqueue time, full garbage collections inside the timed steps
 """
@@ -29,6 +30,9 @@ def main():
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=576)
     ap.add_argument("--frames", type=int, default=14)
+    ap.add_argument("--batch", type=int, default=1, help="clips per step (--per_gpu_batch_size): every clip its own latents, embedding, trajectories")
+    ap.add_argument("--batch-kernels", type=int, default=0, metavar="B",
+                    help="time ptb_add_rowvec_interleaved_f16 / ptb_colsum_interleaved_f16 (and its two-launch form) alone at [B frames h w, 320] and exit")
     ap.add_argument("--tiny", action="store_true", help="the test-sized networks (plumbing check)")
     ap.add_argument("--gemm-table", action="store_true", help="per-shape table of the pt_gemm_f16 launches of one step")
     ap.add_argument("--igemm-table", action="store_true", help="per-shape table of the pt_igemm_f16 launches of one step (forward + data gradients)")
@@ -62,6 +66,8 @@ def main():
     dev = torch.device("cuda:0")
     if a.optimizer_launch:
         return optimizer_launch(a.optimizer_launch, a.tiny, dev)
+    if a.batch_kernels:
+        return batch_kernels(a.batch_kernels, a.frames, (a.height // 8) * (a.width // 8), 320, dev)
     cfg = dict(num_attention_heads=(5, 10, 20, 20), num_frames=a.frames)
     ce = (16, 32, 96, 256)
     if a.tiny:
@@ -88,10 +94,10 @@ def main():
           f"{' + EMA shadow, ' + a.ema if a.ema != 'off' else ''})", file=sys.stderr if a.json else sys.stdout)
     h, w = a.height // 8, a.width // 8
     D = unet.config.cross_attention_dim
-    lat = torch.randn(1, a.frames, 4, h, w, generator=g) * 0.18215 * 5
-    emb = torch.randn(1, 1, D, generator=g)
-    traj = torch.rand(1, a.frames, 3, a.height, a.width, generator=g) * 2 - 1
-    mv = torch.tensor([127.0])
+    lat = torch.randn(a.batch, a.frames, 4, h, w, generator=g) * 0.18215 * 5
+    emb = torch.randn(a.batch, 1, D, generator=g)
+    traj = torch.rand(a.batch, a.frames, 3, a.height, a.width, generator=g) * 2 - 1
+    mv = torch.full((a.batch,), 127.0)
     gen = torch.Generator().manual_seed(5)
     L = hip.lib()
     for _ in range(a.warmup):
@@ -133,7 +139,7 @@ def main():
             flops += fl.value
         L.pt_prof_enable(0)
         med = sorted(tt)[len(tt) // 2]
-        print(json.dumps({"ms_per_step": round(1000 * med, 1), "clips_per_s": round(1.0 / med, 2), "ms_per_step_all": [round(1000 * v, 1) for v in tt],
+        print(json.dumps({"ms_per_step": round(1000 * med, 1), "clips_per_s": round(a.batch / med, 2), **({"batch": a.batch} if a.batch != 1 else {}), "ms_per_step_all": [round(1000 * v, 1) for v in tt],
                           "host_enqueue_ms": round(sorted(host)[len(host) // 2], 1),
                           "matrix_TFLOP_per_step": round(flops / 1e12, 2), "peak_device_GiB": round(peak, 1),
                           "trainable_params_M": round(tr.params.numel / 1e6, 1), "loss_finite": bool(out["loss"] == out["loss"]),
@@ -195,7 +201,7 @@ def main():
         for sh, (n, m, f) in list(sorted(agg.items(), key=lambda kv: -kv[1][1]))[:45]:
             M_, N_, K_, kh, kw, st, up, c1, act, epi = sh
             print(f"  {M_:8d} {N_:6d} {K_:6d} {kh}x{kw} {st} {up} {c1:5d} {act} {epi} {n:4d} {m:9.3f} {100 * m / tot:6.2f} {f / m / 1e9:8.1f}")
-    print(f"{a.frames} x {a.height} x {a.width}, batch 1: {dt * 1e3:.1f} ms per training step (wall, incl. host; prof events on); "
+    print(f"{a.frames} x {a.height} x {a.width}, batch {a.batch}: {dt * 1e3:.1f} ms per training step (wall, incl. host; prof events on); "
           f"loss {out['loss']:.4f}, grad norm {out.get('grad_norm', float('nan')):.3e}, stepped {out['stepped']}, loss scale {tr.loss_scale:g}")
     tot_fl = 0.0
     for name, (n, ms, fl) in fam.items():
@@ -203,6 +209,34 @@ def main():
         print(f"  {name:22s} {n:8.0f} launches  {ms:9.2f} ms  {fl / 1e12:8.2f} TFLOP  {fl / max(ms, 1e-9) / 1e9:8.1f} TFLOP/s")
     print(f"  matrix flops per step {tot_fl / 1e12:.1f} TFLOP -> {tot_fl / dt / 1e12:.0f} TFLOP/s over the whole step; "
           f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
+
+
+def batch_kernels(B: int, F: int, S: int, Cc: int, dev) -> None:
+    """The temporal blocks' cross-attention rows of a batch (include/posetraj_batch.h) alone: hipEvent time per launch, median of 20
+    behind 5 warm-up launches, and the bytes each moves (add: x read + y written; reductions: dy read)."""
+    from posetraj_amd import hip, ops
+    L, st = hip.checked(), ops._stream()
+    rows = B * F * S
+    x, dy = torch.randn(rows, Cc, device=dev).half(), torch.randn(rows, Cc, device=dev).half()
+    vec, y = torch.randn(B, Cc, device=dev).half(), torch.empty(rows, Cc, dtype=torch.float16, device=dev)
+    out = torch.zeros(B, Cc, device=dev)
+    ws = torch.empty(max(L.ptb_colsum_interleaved_ws_floats(B, F, S, Cc), 2), device=dev)
+    legs = (("ptb_add_rowvec_interleaved_f16", 4 * rows * Cc, lambda: L.ptb_add_rowvec_interleaved_f16(x.data_ptr(), vec.data_ptr(), B, F, S, Cc, y.data_ptr(), st)),
+            ("ptb_colsum_interleaved_f16", 2 * rows * Cc, lambda: L.ptb_colsum_interleaved_f16(dy.data_ptr(), B, F, S, Cc, out.data_ptr(), st)),
+            ("ptb_colsum_interleaved_det_f16", 2 * rows * Cc, lambda: L.ptb_colsum_interleaved_det_f16(dy.data_ptr(), B, F, S, Cc, out.data_ptr(), ws.data_ptr(), ws.numel(), st)),
+            ("pt_add_rowvec_f16 (same bytes)", 4 * rows * Cc, lambda: L.pt_add_rowvec_f16(x.data_ptr(), vec.data_ptr(), rows, Cc, F * S, y.data_ptr(), st)),
+            ("pt_colsum_f16 (same bytes)", 2 * rows * Cc, lambda: L.pt_colsum_f16(dy.data_ptr(), F * S, B, Cc, Cc, out.data_ptr(), st)))
+    for name, nbytes, fn in legs:
+        tt = []
+        for i in range(25):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            tt.append(e0.elapsed_time(e1))
+        us = 1e3 * sorted(tt[5:])[10]
+        print(f"  {name:34s} [{B} x {F} x {S}, {Cc}]  {us:8.1f} us  {nbytes / us / 1e6:6.2f} TB/s")
 
 
 def optimizer_launch(rounds: int, tiny: bool, dev) -> None:
