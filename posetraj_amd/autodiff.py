@@ -206,8 +206,8 @@ def _split_k(tiles: int, K: int) -> int:
 
 # ------------------------------------------------------------------------------------------------- parameters
 class ParamStore:
-    """The trainable network's parameters as ONE flat fp32 buffer (+ gradient and Adam moments): named views for the layers,
-    one launch for the optimizer.  ``version`` counts optimizer steps: layers re-pack their fp16 operands when it moves.
+    """The trainable network's parameters as ONE flat fp32 buffer (+ gradient; the optimizer's state lies in the same layout,
+    ``optim.py``): named views for the layers, one launch for the optimizer.  ``version`` counts optimizer steps: layers re-pack their fp16 operands when it moves.
 
     Convolution weights are kept TAP-MAJOR, ``[kh kw][Co][Ci]`` instead of torch's ``[Co][Ci][kh][kw]``: a weight gradient is
     then one ``[Co, Ci]`` matrix per tap, written with unit stride by ``pt_gemm_f16`` (in torch's layout neighbouring input
@@ -215,9 +215,7 @@ class ParamStore:
     reads whole rows.  ``value()`` / ``gradient()`` return views in torch's shape (permuted strides), so callers never see it;
     AdamW is element-wise and does not care."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], device, use_8bit_adam: bool = False):
-        """``use_8bit_adam``: no full-size moment buffers (``exp_avg`` / ``exp_avg_sq`` are None); ``adam8`` holds the block-quantised
-        state instead (``training_utils.Adam8bitState``)."""
+    def __init__(self, sd: Dict[str, torch.Tensor], device):
         self.names = list(sd)
         self.offsets, n = {}, 0
         for k in self.names:
@@ -226,13 +224,7 @@ class ParamStore:
         self.numel = n
         self.flat = torch.zeros(n, dtype=torch.float32, device=device)
         self.grad = torch.zeros(n, dtype=torch.float32, device=device)
-        self.exp_avg = None if use_8bit_adam else torch.zeros(n, dtype=torch.float32, device=device)
-        self.exp_avg_sq = None if use_8bit_adam else torch.zeros(n, dtype=torch.float32, device=device)
         self.shapes = {k: tuple(sd[k].shape) for k in self.names}
-        self.adam8 = None
-        if use_8bit_adam:
-            from .training_utils import Adam8bitState
-            self.adam8 = Adam8bitState(self)
         for k in self.names:
             self.value(k).copy_(sd[k].to(device=device, dtype=torch.float32))
         self.version, self.trainable = 0, True
@@ -272,6 +264,11 @@ class ParamStore:
             self.flat16.copy_(self.flat)
             self._mirror_version = self.version
         return self._view(self.flat16, k)
+
+    def moved_with_mirror(self) -> None:
+        """The master moved and the same pass wrote the fp16 mirror (the optimizer's launch): ``half_view()`` need not cast again."""
+        self.version += 1
+        self._mirror_version = self.version
 
     def scalar(self, k) -> float:
         """A one-element parameter's value on the host; all of them travel in ONE copy per optimizer step."""

@@ -8,7 +8,8 @@ No tensor arithmetic happens here: files, counters and a scalar multiplier.  A c
     controlnet/config.json, controlnet/diffusion_pytorch_model.safetensors    what ``model.save_pretrained`` writes from the
                                                                                save hook: the fp32 master parameters, torch layout,
                                                                                readable by ``ControlNetSDVModel.from_pretrained``
-    optimizer.safetensors            ``exp_avg.<name>`` / ``exp_avg_sq.<name>``: AdamW's moments per parameter, torch layout.  With
+    optimizer.safetensors            ``trainer.optimizer.state_dict()`` (``optim.py``).  ``exp_avg.<name>`` / ``exp_avg_sq.<name>``:
+                                     AdamW's moments per parameter, torch layout.  With
                                      ``ControlNetTrainer(use_8bit_adam=True)``: ``state1.`` / ``state2.<name>`` (uint8 codes, STORED
                                      order) and ``absmax1.`` / ``absmax2.<name>`` (one per block of 256) for parameters of at least
                                      4096 elements, ``exp_avg.`` / ``exp_avg_sq.<name>`` for the smaller ones, and the two books
@@ -168,23 +169,13 @@ def save_state(trainer, output_dir: str) -> None:
         raise RuntimeError("save_state inside an accumulation cycle: the accumulated gradients are not part of a checkpoint")
     os.makedirs(output_dir, exist_ok=True)
     save_controlnet(trainer, os.path.join(output_dir, "controlnet"))
-    P = trainer.params
-    adam8 = getattr(P, "adam8", None)
-    if adam8 is not None:
-        moments = adam8.state_dict()
-    else:
-        moments = {}
-        for kind, buf in (("exp_avg", P.exp_avg), ("exp_avg_sq", P.exp_avg_sq)):
-            for k, v in P.export(buf).items():
-                moments[f"{kind}.{k}"] = v.cpu()
-    save_file(moments, os.path.join(output_dir, "optimizer.safetensors"))
+    save_file(trainer.optimizer.state_dict(), os.path.join(output_dir, "optimizer.safetensors"))
     state = {"format": 1, "optimizer_steps": trainer.optimizer_steps, "skipped_steps": trainer.skipped_steps, "loss_scale": trainer.loss_scale,
              "growth_tracker": trainer._clean, "growth_interval": trainer.growth_interval, "micro_batch": trainer._micro,
              "hyperparameters": {"learning_rate": trainer.lr, "adam_beta1": trainer.betas[0], "adam_beta2": trainer.betas[1],
                                  "adam_weight_decay": trainer.weight_decay, "adam_epsilon": trainer.eps,
                                  "gradient_accumulation_steps": trainer.accumulation}}
-    if adam8 is not None:                                                  # (a checkpoint of the fp32 optimizer has neither key)
-        state["optimizer"], state["optimizer_block_size"] = "adamw8bit", adam8.plan["block"]
+    state.update(trainer.optimizer.checkpoint_meta())                      # the 8-bit kind and its block size; nothing for the fp32 optimizer
     ema = getattr(trainer, "ema", None)
     if ema is not None:                                                    # the save hook's `ema.save_pretrained` (:993-994)
         ema.save_pretrained(os.path.join(output_dir, "controlnet_ema"))
@@ -205,13 +196,7 @@ def load_state(trainer, input_dir: str) -> dict:
     if state.get("format") != 1:
         raise RuntimeError(f"{input_dir}: unknown trainer_state format {state.get('format')!r}")
     P = trainer.params
-    adam8 = getattr(P, "adam8", None)
-    have, want = state.get("optimizer", "adamw"), "adamw8bit" if adam8 is not None else "adamw"
-    if have != want:
-        raise ValueError(f"{input_dir}: the checkpoint holds the state of optimizer {have!r} but the trainer runs {want!r} "
-                         f"(use_8bit_adam={adam8 is not None}); states of 'adamw' and 'adamw8bit' are not converted into each other")
-    if adam8 is not None and state.get("optimizer_block_size") != adam8.plan["block"]:
-        raise ValueError(f"{input_dir}: 8-bit optimizer state in blocks of {state.get('optimizer_block_size')!r}, this build uses {adam8.plan['block']}")
+    trainer.optimizer.check_checkpoint_meta(state, input_dir)              # the other optimizer kind, another block size: refused
     ema = getattr(trainer, "ema", None)
     ema_dir = os.path.join(input_dir, "controlnet_ema")
     if ema is not None and not os.path.isdir(ema_dir):                     # (a trainer without EMA ignores the folder, as the script does without the flag)
@@ -220,11 +205,7 @@ def load_state(trainer, input_dir: str) -> dict:
     weights = load_file(os.path.join(input_dir, "controlnet", "diffusion_pytorch_model.safetensors"))
     moments = load_file(os.path.join(input_dir, "optimizer.safetensors"))
     P.load(P.flat, weights)
-    if adam8 is not None:
-        adam8.load_state_dict(moments)
-    else:
-        P.load(P.exp_avg, {k[len("exp_avg."):]: v for k, v in moments.items() if k.startswith("exp_avg.")})
-        P.load(P.exp_avg_sq, {k[len("exp_avg_sq."):]: v for k, v in moments.items() if k.startswith("exp_avg_sq.")})
+    trainer.optimizer.load_state_dict(moments)
     P.version += 1                                                         # layers re-pack their fp16 operands from the new master
     P.zero_grad()
     trainer.optimizer_steps, trainer.skipped_steps = int(state["optimizer_steps"]), int(state["skipped_steps"])

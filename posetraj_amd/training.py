@@ -10,7 +10,8 @@ package's own models; their outputs are the step's inputs.  The camera twin (``c
 ``camera_cond`` and without the spatial loss) trains through the same class.  ``--use_ema`` (off in the launch scripts) is
 ``ControlNetTrainer(use_ema=True)``: diffusers' ``EMAModel`` over the ControlNet's parameters (``training_utils.py``), stepped inside
 the optimizer's pass.  ``--use_8bit_adam`` (``:1041-1049``, bitsandbytes' ``AdamW8bit``; off in the launch scripts) is
-``ControlNetTrainer(use_8bit_adam=True)``: block-quantised moments, updated by ``pto_adamw8_f32``.  ``--gradient_checkpointing``
+``ControlNetTrainer(use_8bit_adam=True)``: block-quantised moments, updated by ``pto_adamw8_f32``; either way ``trainer.optimizer``
+(``optim.py``) owns the moments, the update's launch and the optimizer's part of a checkpoint.  ``--gradient_checkpointing``
 (``:1025-1026``, ON in every launch script) is ``ControlNetTrainer(gradient_checkpointing=True)``: every residual block and transformer
 of the ControlNet is a checkpointed segment of the tape (``autodiff.checkpoint``) - its activations are dropped after the forward and
 recomputed, by the same kernels, in the reverse pass.  Not here: the data loader.
@@ -24,7 +25,7 @@ from typing import Optional
 
 import torch
 
-from . import hip, ops
+from . import hip, ops, optim
 
 # scripts/train_svd_traj_VIPSeg_14.py:314-319, :1288
 MIN_VALUE, MAX_VALUE, IMAGE_D, NOISE_D_LOW, NOISE_D_HIGH, SIGMA_DATA = 0.002, 700, 64, 32, 64, 0.5
@@ -259,8 +260,8 @@ class ControlNetTrainer:
 
     ``use_8bit_adam`` (``--use_8bit_adam``): AdamW's two moments are kept as 8-bit codes into two 256-entry books with one fp32
     absmax per block of 256 stored elements (parameters under 4096 elements keep fp32 moments) - 2.03 bytes per parameter instead of
-    8; the full-size ``exp_avg`` / ``exp_avg_sq`` buffers are not allocated (``params.adam8`` holds the state,
-    ``training_utils.Adam8bitState``).  ``optimizer_step`` runs ``pto_adamw8_f32`` - torch's AdamW statements on the dequantised moments,
+    8; ``trainer.optimizer`` is then an ``optim.AdamW8bit`` instead of an ``optim.AdamW``, and no full-size moment buffer is
+    allocated.  Its ``step`` runs ``pto_adamw8_f32`` - torch's AdamW statements on the dequantised moments,
     the fp16 mirror, the gradient's zeroing and the fused EMA in one launch, as the fp32 pass does - under the same GradScaler rules,
     schedule and pack stream.  The format restates bitsandbytes' published blockwise quantisation; parity with the package is not
     pinned.  Data parallel needs nothing new: the update is a deterministic function of the averaged gradients, so every
@@ -335,12 +336,14 @@ class ControlNetTrainer:
         cfg = dict(controlnet_config)
         self.unet, self.device, self.config = unet, dev, cfg
         self.use_8bit_adam = bool(use_8bit_adam)
-        self.params = AD.ParamStore(controlnet_state_dict, dev, use_8bit_adam=self.use_8bit_adam)
+        self.params = AD.ParamStore(controlnet_state_dict, dev)
+        self.lr, self.betas, self.weight_decay, self.eps = learning_rate, (adam_beta1, adam_beta2), adam_weight_decay, adam_epsilon
+        self.optimizer = (optim.AdamW8bit if self.use_8bit_adam else optim.AdamW)(self.params, lr=self.lr, betas=self.betas, eps=self.eps,
+                                                                                 weight_decay=self.weight_decay)
         self.deterministic = self.params.deterministic = bool(deterministic)
         self.controlnet = TG.ControlNetGraph(self.params, cfg)
         self._frozen = AD.FrozenParams({k: v for k, v in unet.state_dict().items() if k.startswith(("up_blocks.", "conv_norm_out.", "conv_out."))}, dev)
         self.decoder = TG.UNetDecoderGraph(self._frozen, dict(unet.config))
-        self.lr, self.betas, self.weight_decay, self.eps = learning_rate, (adam_beta1, adam_beta2), adam_weight_decay, adam_epsilon
         self.accumulation, self.loss_scale, self.growth_interval = int(gradient_accumulation_steps), float(loss_scale), int(growth_interval)
         self.scaling_factor, self.dropout = scaling_factor, conditioning_dropout_prob
         self.optimizer_steps, self.skipped_steps, self._micro, self._clean = 0, 0, 0, 0
@@ -626,24 +629,13 @@ class ControlNetTrainer:
             self.optimizer_steps += 1
             P = self.params
             inv_scale = 1.0 / (self._accum_scale * self.world)
-            if P.adam8 is not None:                       # the same pass over block-quantised moments (and the EMA, when it is fused)
-                fused = ema is not None and self.ema_fused
-                P.adam8.step(self.last_lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, inv_scale,
-                             ema.shadow if fused else None, omd if fused else 0.0)
-                if ema is not None and not fused:
-                    ema.update(omd)
-            else:
-                # AdamW + the fp16 mirror of the new parameters + the gradient's zeroing in ONE pass over the buffers
-                adamw = (P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), P.numel, self.last_lr, self.betas[0],
-                         self.betas[1], self.eps, self.weight_decay, self.optimizer_steps, inv_scale, P.flat16.data_ptr(), 1)
-                if ema is not None and self.ema_fused:    # ... and the EMA of the new parameters in the same pass
-                    hip.checked().pt_adamw_ema_f32(*adamw, ema.shadow.data_ptr(), omd, ops._stream())
-                else:
-                    hip.checked().pt_adamw_fused_f32(*adamw, ops._stream())
-                    if ema is not None:
-                        ema.update(omd)
-            P.version += 1
-            P._mirror_version = P.version                 # (half_view() need not cast the buffer again)
+            # AdamW + the fp16 mirror of the new parameters + the gradient's zeroing in ONE pass over the buffers - and the EMA of the
+            # new parameters in the same pass, when it is fused
+            fused = ema is not None and self.ema_fused
+            self.optimizer.step(self.last_lr, self.optimizer_steps, inv_scale, ema.shadow if fused else None, omd if fused else 0.0)
+            if ema is not None and not fused:
+                ema.update(omd)
+            P.moved_with_mirror()                         # (half_view() need not cast the buffer again)
             if self.pack_stream and self._packs_built and not self.use_graph:
                 # the new weights' fp16 packs, all layers at once, on a stream of their own behind AdamW (the next step's ControlNet
                 # forward waits for it; the frozen encoder, the input staging and the host's bookkeeping do not)

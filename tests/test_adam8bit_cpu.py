@@ -22,7 +22,7 @@ def _store(counts):
 
 @pytest.mark.parametrize("signed", [True, False])
 def test_books(signed):
-    from posetraj_amd.training_utils import create_dynamic_map
+    from posetraj_amd.optim import create_dynamic_map
     b = create_dynamic_map(signed)
     assert b.dtype == torch.float32 and b.shape == (256,)
     v = b.tolist()
@@ -37,7 +37,7 @@ def test_books(signed):
 
 
 def test_planner_on_a_hand_made_list():
-    from posetraj_amd.training_utils import ADAM8_BLOCK, ADAM8_MIN_SIZE, plan_8bit_state
+    from posetraj_amd.optim import ADAM8_BLOCK, ADAM8_MIN_SIZE, plan_8bit_state
     names, shapes, offsets, n = _store(HAND)
     plan = plan_8bit_state(names, shapes, offsets)
     assert (ADAM8_BLOCK, ADAM8_MIN_SIZE, plan["block"]) == (256, 4096, 256)
@@ -75,7 +75,7 @@ def test_planner_on_a_hand_made_list():
 
 def test_full_width_controlnet_state_is_a_quarter_of_the_fp32_moments():
     from posetraj_amd.controlnet_sdv import ControlNetSDVModel
-    from posetraj_amd.training_utils import plan_8bit_state
+    from posetraj_amd.optim import plan_8bit_state
     spec = ControlNetSDVModel().param_spec()
     names = list(spec)
     shapes = {k: tuple(spec[k]) for k in names}
@@ -142,7 +142,7 @@ def test_checkpoint_of_the_8bit_state_round_trips_and_the_kinds_do_not_mix(tmp_p
     """``save_state`` / ``load_state`` over a CPU-resident store: the file set, the keys of ``optimizer.safetensors``, the stored
     order of the codes, torch's order of a small convolution's fp32 moments, and the refusal to load the other kind."""
     from safetensors.torch import load_file
-    from posetraj_amd import train_state as TS
+    from posetraj_amd import optim, train_state as TS
     from posetraj_amd.autodiff import ParamStore
     g = torch.Generator().manual_seed(0)
     sd = {"conv_in.weight": torch.randn(6, 5, 3, 3, generator=g), "conv_in.bias": torch.randn(6, generator=g),
@@ -150,13 +150,15 @@ def test_checkpoint_of_the_8bit_state_round_trips_and_the_kinds_do_not_mix(tmp_p
           "mid.mix_factor": torch.tensor([0.25])}
 
     def trainer(eight):
-        P = ParamStore(sd, "cpu", use_8bit_adam=eight)
-        return types.SimpleNamespace(params=P, config={"in_channels": 5}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0, _clean=0,
+        P = ParamStore(sd, "cpu")
+        opt = (optim.AdamW8bit if eight else optim.AdamW)(P, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+        return types.SimpleNamespace(params=P, optimizer=opt, config={"in_channels": 5}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0, _clean=0,
                                      growth_interval=2000, _micro=0, _accum_scale=None, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8,
                                      accumulation=1)
     a = trainer(True)
-    A = a.params.adam8
-    assert a.params.exp_avg is None and a.params.exp_avg_sq is None
+    A = a.optimizer
+    assert A.kind == "adamw8bit" and A.exp_avg.numel() == A.exp_avg_sq.numel() == A.plan["n_f32_alloc"] < a.params.numel      # no full-size moment buffer
+    assert not any(hasattr(a.params, name) for name in ("exp_avg", "exp_avg_sq", "adam8"))
     assert A.zero_codes == (127, 0) and bool((A.state1 == 127).all()) and bool((A.state2 == 0).all()) and float(A.absmax1.abs().sum()) == 0.0
     assert A.table.numel() == 32 * len(sd) and A.state1.numel() == 256 * A.plan["n_blocks"]
     A.state1.copy_(torch.randint(0, 256, A.state1.shape, generator=g, dtype=torch.uint8))
@@ -184,7 +186,7 @@ def test_checkpoint_of_the_8bit_state_round_trips_and_the_kinds_do_not_mix(tmp_p
     assert torch.equal(m["qmap1"], A.qmap1) and torch.equal(m["qmap2"], A.qmap2)
     b = trainer(True)
     TS.load_state(b, ck)
-    B = b.params.adam8
+    B = b.optimizer
     assert b.optimizer_steps == 7
     for k in sd:
         for x, y in zip(A._slices(k), B._slices(k)):

@@ -101,7 +101,7 @@ class Case:
 
     def __init__(self, counts, dev, seed=0, zero_state=False, sentinel=True):
         from posetraj_amd import hip
-        from posetraj_amd.training_utils import create_dynamic_map, plan_8bit_state
+        from posetraj_amd.optim import create_dynamic_map, plan_8bit_state
         g = torch.Generator().manual_seed(seed)
         names = [f"p{i}" for i in range(len(counts))]
         shapes, offsets, n = {}, {}, 0
@@ -361,7 +361,7 @@ def run(dev, golden, tmp_path_factory):
     kw = dict(learning_rate=2e-4, conditioning_dropout_prob=0.1, loss_scale=4096.0)
     tr = ControlNetTrainer(cfg, sd0, un, **kw, use_8bit_adam=True)
     fp = ControlNetTrainer(cfg, sd0, un, **kw)
-    P, A = tr.params, tr.params.adam8
+    P, A = tr.params, tr.optimizer
     ck = str(tmp_path_factory.mktemp("adam8") / "checkpoint-2")
     ck32 = str(tmp_path_factory.mktemp("adam8") / "checkpoint-1")
     steps = []
@@ -390,8 +390,9 @@ DRIFT_RECORDED = 1.308e-4    # relative L2 distance from the fp32 trainer after 
 
 def test_three_trainer_steps_follow_the_restatement(run):
     tr = run["tr"]
-    P, A = tr.params, tr.params.adam8
-    assert P.exp_avg is None and P.exp_avg_sq is None and (tr.optimizer_steps, tr.skipped_steps) == (3, 0)
+    P, A = tr.params, tr.optimizer
+    assert A.kind == "adamw8bit" and A.exp_avg.numel() == A.exp_avg_sq.numel() == A.plan["n_f32_alloc"] < P.numel      # no full-size moment buffer
+    assert not any(hasattr(P, name) for name in ("exp_avg", "exp_avg_sq", "adam8")) and (tr.optimizer_steps, tr.skipped_steps) == (3, 0)
     live = torch.zeros(P.numel, dtype=torch.bool)
     for k, (o, n) in P.spans().items():
         live[o:o + n] = True
@@ -419,7 +420,7 @@ def test_a_forced_skip_leaves_parameters_and_state_alone(run, dev):
     un, cfg, sd0, kw = run["nets"]
     tr = ControlNetTrainer(cfg, sd0, un, **kw, use_8bit_adam=True, use_ema=True)
     assert tr.step(*run["batch"], **run["draws"])["stepped"] is True                                 # a state that is not all zeros
-    A = tr.params.adam8
+    A = tr.optimizer
     p0, s0, st0 = tr.params.flat.clone(), tr.ema.shadow.clone(), {k: v.clone() for k, v in A.state_dict().items()}
     tr.loss_and_grads(*run["batch"], **run["draws"])
     assert tr.optimizer_step(grad_norm=float("inf")) is False
@@ -445,7 +446,7 @@ def test_fused_and_separate_ema_give_the_same_numbers(run, dev):
         assert x.optimizer_step() is True and y.optimizer_step() is True
         assert torch.equal(x.params.flat, y.params.flat) and torch.equal(x.ema.shadow, y.ema.shadow), i
         assert not torch.equal(x.ema.shadow, x.params.flat) or i == 0
-    sx, sy = x.params.adam8.state_dict(), y.params.adam8.state_dict()
+    sx, sy = x.optimizer.state_dict(), y.optimizer.state_dict()
     assert all(torch.equal(sx[k], sy[k]) for k in sx)
 
 
@@ -459,10 +460,12 @@ def test_memory_the_full_size_moments_are_gone(run, dev):
     before = torch.cuda.memory_allocated()
     b = ControlNetTrainer(cfg, sd0, un, **kw, use_8bit_adam=True)
     grown8 = torch.cuda.memory_allocated() - before
-    n, state_bytes = b.params.numel, b.params.adam8.plan["state_bytes"]
+    n, state_bytes = b.params.numel, b.optimizer.plan["state_bytes"]
     print(f"memory: fp32 trainer {grown32} B, 8-bit trainer {grown8} B, difference {grown32 - grown8} B, planner says {8 * n - state_bytes} B")
     assert abs((grown32 - grown8) - (8 * n - state_bytes)) < (1 << 21)
-    assert b.params.exp_avg is None and a.params.exp_avg.numel() == n and a.params.adam8 is None
+    assert b.optimizer.kind == "adamw8bit" and b.optimizer.exp_avg.numel() == b.optimizer.plan["n_f32_alloc"] < n
+    assert not any(hasattr(t.params, name) for t in (a, b) for name in ("exp_avg", "exp_avg_sq", "adam8"))
+    assert a.optimizer.exp_avg.numel() == n and a.optimizer.kind == "adamw"
     assert 8 * n - state_bytes > 0.7 * 8 * n
 
 
@@ -478,7 +481,7 @@ def test_resume_continues_bit_for_bit_and_the_kinds_do_not_mix(run, dev):
     b.load_state(ck)
     third = run["steps"][2]
     assert b.optimizer_steps == 2 and torch.equal(b.params.flat.cpu(), third["p"])
-    deq = b.params.adam8.dequantize()
+    deq = b.optimizer.dequantize()
     assert torch.equal(deq[0].cpu(), third["deq"][0]) and torch.equal(deq[1].cpu(), third["deq"][1])
     b.loss_and_grads(*run["batch"], **run["draws"])
     same = torch.equal(b.params.grad, third["raw_grad"])
@@ -486,7 +489,7 @@ def test_resume_continues_bit_for_bit_and_the_kinds_do_not_mix(run, dev):
     b.params.grad.copy_(third["raw_grad"])                    # the step under test is the optimizer's: both runs take it on the same gradients
     assert b.optimizer_step() is True
     assert torch.equal(b.params.flat.cpu(), third["p_new"])
-    got = b.params.adam8.state_dict()
+    got = b.optimizer.state_dict()
     assert set(got) == set(third["state"]) and all(torch.equal(got[k], third["state"][k]) for k in got)
     with pytest.raises(ValueError, match="'adamw8bit'.*'adamw'"):
         ControlNetTrainer(cfg, sd0, un, **kw).load_state(ck)

@@ -871,7 +871,7 @@ def test_checkpoint_resume_and_lr_schedule(dev, golden, tmp_path):
     print(f"resumed vs continuous run after the third step: |diff| {diff:.2e} of |moved| {moved:.2e}, max element diff {worst:.2e} (lr {lr:g})")
     assert diff < 1e-2 * moved and worst <= 2 * lr       # a near-zero gradient's sign may fall either way under fp32 atomics
     # the moments, over the whole store (a tensor whose gradient is rounding noise has noise for moments: no per-tensor bound)
-    for buf_a, buf_b in ((a.params.exp_avg, b.params.exp_avg), (a.params.exp_avg_sq, b.params.exp_avg_sq)):
+    for buf_a, buf_b in ((a.optimizer.exp_avg, b.optimizer.exp_avg), (a.optimizer.exp_avg_sq, b.optimizer.exp_avg_sq)):
         assert float((buf_a - buf_b).double().norm() / buf_a.double().norm()) < 1e-3
     # the controlnet/ folder is a diffusers-format model of the parameters at save time
     m = ControlNetSDVModel.from_pretrained(ck, subfolder="controlnet", device=dev, keep_source=True)

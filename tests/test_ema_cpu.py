@@ -28,10 +28,12 @@ def _sd():
 
 def _trainer(use_ema, **ema_kw):
     """The attribute-less stand-in of tests/test_host_cpu.py, with or without an ``ema``."""
+    from posetraj_amd import optim
     from posetraj_amd.autodiff import ParamStore
     from posetraj_amd.training_utils import EMAModel
     P = ParamStore(_sd(), "cpu")
-    t = types.SimpleNamespace(params=P, config={"in_channels": 5, "_name_or_path": "x"}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0,
+    opt = optim.AdamW(P, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    t = types.SimpleNamespace(params=P, optimizer=opt, config={"in_channels": 5, "_name_or_path": "x"}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0,
                               _clean=0, growth_interval=2000, _micro=0, _accum_scale=None, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-2,
                               eps=1e-8, accumulation=2)
     if use_ema:

@@ -552,7 +552,7 @@ def test_trainer_state_files_round_trip(tmp_path):
     tensors under the reference's names, strictness of the loader, counters."""
     import types
     from safetensors.torch import load_file
-    from posetraj_amd import train_state as TS
+    from posetraj_amd import optim, train_state as TS
     from posetraj_amd.autodiff import ParamStore
     g = torch.Generator().manual_seed(0)
     sd = {"conv_in.weight": torch.randn(6, 5, 3, 3, generator=g), "conv_in.bias": torch.randn(6, generator=g),
@@ -560,12 +560,13 @@ def test_trainer_state_files_round_trip(tmp_path):
 
     def trainer():
         P = ParamStore(sd, "cpu")
-        return types.SimpleNamespace(params=P, config={"in_channels": 5, "_name_or_path": "x"}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0,
+        opt = optim.AdamW(P, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+        return types.SimpleNamespace(params=P, optimizer=opt, config={"in_channels": 5, "_name_or_path": "x"}, optimizer_steps=0, skipped_steps=0, loss_scale=65536.0,
                                      _clean=0, growth_interval=2000, _micro=0, _accum_scale=None, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-2,
                                      eps=1e-8, accumulation=2)
     a = trainer()
-    a.params.exp_avg.copy_(torch.randn(a.params.numel, generator=g))
-    a.params.exp_avg_sq.copy_(torch.rand(a.params.numel, generator=g))
+    a.optimizer.exp_avg.copy_(torch.randn(a.params.numel, generator=g))
+    a.optimizer.exp_avg_sq.copy_(torch.rand(a.params.numel, generator=g))
     a.params.flat.mul_(1.5)
     a.optimizer_steps, a.skipped_steps, a.loss_scale, a._clean = 4000, 3, 32768.0, 17
     ck = str(tmp_path / "checkpoint-4000")
@@ -581,7 +582,7 @@ def test_trainer_state_files_round_trip(tmp_path):
     assert state["hyperparameters"]["gradient_accumulation_steps"] == 2
     assert (b.optimizer_steps, b.skipped_steps, b.loss_scale, b._clean, b._micro) == (4000, 3, 32768.0, 17, 0) and b.params.version == 1
     for k in sd:                                                  # padding between parameters is not part of the state
-        for buf_a, buf_b in ((a.params.flat, b.params.flat), (a.params.exp_avg, b.params.exp_avg), (a.params.exp_avg_sq, b.params.exp_avg_sq)):
+        for buf_a, buf_b in ((a.params.flat, b.params.flat), (a.optimizer.exp_avg, b.optimizer.exp_avg), (a.optimizer.exp_avg_sq, b.optimizer.exp_avg_sq)):
             assert torch.equal(a.params.raw(buf_a, k), b.params.raw(buf_b, k))
     a._micro = 1
     with pytest.raises(RuntimeError, match="accumulation cycle"):

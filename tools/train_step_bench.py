@@ -14,6 +14,7 @@ the memory high-water mark.
 """
 import argparse
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -89,7 +90,7 @@ def main():
                            use_ema=a.ema != "off", use_8bit_adam=a.optimizer == "adamw8bit",
                            gradient_checkpointing={"off": False, "controlnet": True, "all": "all"}[a.gradient_checkpointing], deterministic=a.deterministic)
     tr.ema_fused = a.ema != "separate"
-    moments = "2 Adam moments" if tr.params.adam8 is None else f"8-bit Adam state, {tr.params.adam8.plan['state_bytes'] / 2 ** 20:.0f} MiB"
+    moments = "2 Adam moments" if tr.optimizer.kind == "adamw" else f"8-bit Adam state, {tr.optimizer.state_bytes / 2 ** 20:.0f} MiB"
     print(f"set-up {time.time() - t0:.1f} s; {tr.params.numel / 1e6:.1f} M trainable parameters (fp32 master + gradient + {moments}"
           f"{' + EMA shadow, ' + a.ema if a.ema != 'off' else ''})", file=sys.stderr if a.json else sys.stdout)
     h, w = a.height // 8, a.width // 8
@@ -243,54 +244,35 @@ def optimizer_launch(rounds: int, tiny: bool, dev) -> None:
     """The optimizer's launch alone over a store with the ControlNet's parameter inventory (random values, no network): the fp32 pass
     and the 8-bit pass, without and with the fused EMA, `rounds` interleaved rounds of 5 launches behind 2 warm-up launches each;
     hipEvent time per launch, median of each round."""
-    from posetraj_amd import ControlNetSDVModel, hip, ops
-    from posetraj_amd.autodiff import ParamStore
+    import types
+    from posetraj_amd import ControlNetSDVModel, optim
     kw = dict(block_out_channels=(64, 64, 128, 128), num_attention_heads=(1, 1, 2, 2), cross_attention_dim=16, addition_time_embed_dim=8,
               projection_class_embeddings_input_dim=24, layers_per_block=1, conditioning_embedding_out_channels=(8, 8, 16, 32)) if tiny else \
         dict(num_attention_heads=(5, 10, 20, 20))
     spec = ControlNetSDVModel(**kw).param_spec()
 
-    sd = {k: torch.empty(tuple(s), dtype=torch.float16, device="meta") for k, s in spec.items()}
-    stores = {}
-    for name, eight in (("adamw", False), ("adamw8bit", True)):
-        P = ParamStore.__new__(ParamStore)
-        P.names, P.offsets, n = list(sd), {}, 0
-        for k in P.names:
-            P.offsets[k] = n
-            n += (sd[k].numel() + 7) // 8 * 8
-        P.numel, P.shapes = n, {k: tuple(sd[k].shape) for k in P.names}
-        P.flat = torch.randn(n, device=dev) * 0.02
-        P.grad = torch.empty(n, device=dev)
-        P.flat16 = torch.empty(n, dtype=torch.float16, device=dev)
-        if eight:
-            from posetraj_amd.training_utils import Adam8bitState
-            P.adam8 = Adam8bitState(P)
-        else:
-            P.exp_avg, P.exp_avg_sq = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        stores[name] = P
-    shadow = stores["adamw"].flat.clone()
-    n = stores["adamw"].numel
-    A = stores["adamw8bit"].adam8
-    print(f"{n / 1e6:.1f} M parameters in {len(sd)} tensors; 8-bit state {A.plan['state_bytes'] / 2 ** 20:.0f} MiB against {8 * n / 2 ** 20:.0f} MiB "
+    names, shapes, offsets, n = list(spec), {k: tuple(s) for k, s in spec.items()}, {}, 0
+    for k in names:                                            # ParamStore's layout, without the network's values
+        offsets[k] = n
+        n += (math.prod(shapes[k]) + 7) // 8 * 8
+    opts = {}
+    for cls in (optim.AdamW, optim.AdamW8bit):
+        P = types.SimpleNamespace(names=names, shapes=shapes, offsets=offsets, numel=n, flat=torch.randn(n, device=dev) * 0.02,
+                                  grad=torch.empty(n, device=dev), flat16=torch.empty(n, dtype=torch.float16, device=dev))
+        opts[cls.kind] = cls(P, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    shadow = opts["adamw"].params.flat.clone()
+    A = opts["adamw8bit"]
+    print(f"{n / 1e6:.1f} M parameters in {len(names)} tensors; 8-bit state {A.state_bytes / 2 ** 20:.0f} MiB against {opts['adamw'].state_bytes / 2 ** 20:.0f} MiB "
           f"({A.plan['n_blocks']} blocks, {A.plan['n_f32']} elements with fp32 moments)")
-    L, st = hip.checked(), ops._stream()
-    hyper = (1e-5, 0.9, 0.999, 1e-8, 1e-2)
     step = [0]
 
     def launch(which, ema):
-        P = stores[which]
-        P.grad.normal_()                                       # (outside the events) a fresh gradient: the pass zeroes it
+        opt = opts[which]
+        opt.params.grad.normal_()                              # (outside the events) a fresh gradient: the pass zeroes it
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         step[0] += 1
         e0.record()
-        if which == "adamw8bit":
-            P.adam8.step(*hyper, step[0], 1.0, shadow if ema else None, 0.0001)
-        elif ema:
-            L.pt_adamw_ema_f32(P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), n, *hyper, step[0], 1.0,
-                               P.flat16.data_ptr(), 1, shadow.data_ptr(), 0.0001, st)
-        else:
-            L.pt_adamw_fused_f32(P.flat.data_ptr(), P.grad.data_ptr(), P.exp_avg.data_ptr(), P.exp_avg_sq.data_ptr(), n, *hyper, step[0], 1.0,
-                                 P.flat16.data_ptr(), 1, st)
+        opt.step(opt.lr, step[0], 1.0, shadow if ema else None, 0.0001)
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1)
