@@ -191,6 +191,31 @@ class ControlNetSDVModel(HipModel):
         ops.igemm(x_mid, self.controlnet_mid_block, geom=(n, hh, ww), out_scale=conditioning_scale, res=m2, res_post=True, out=m2)
         ops.drop_lo(unet_mid)
 
+    def _accumulate_into_weighted(self, taps, x_mid, conditioning_scale, level_weights, skips, mult, unet_mid):
+        """``_accumulate_into`` with one more factor per (frame, pixel):  skip_j[r] += mult_j * scale * w_l[r] * zero_conv_j(tap_j)[r]
+        (and the same on the mid feature), ``w_l = level_weights[(hh, ww)]`` the fp32 device vector ``[n * hh * ww]`` of the tap's
+        resolution.  The zero-conv writes fp32 into one scratch buffer shared by the 13 taps (``out_f32``, scale 1) and
+        ``ops.weighted_residual_add`` accumulates it in the fused tail's operation order: with all-ones weights the same arithmetic.
+        The weights are READ at run time, so a captured graph follows later in-place edits of the buffers."""
+        if len(skips) != len(taps) or len(mult) != len(taps):
+            raise ValueError(f"{len(taps)} ControlNet taps against {len(skips)} U-Net skips")
+        jobs = [(t, conv, s, m) for t, conv, s, m in zip(taps, self.controlnet_down_blocks, skips, mult) if m]
+        jobs.append((x_mid, self.controlnet_mid_block, unet_mid, 1))
+        for t, _, s, _ in jobs:
+            n, hh, ww, c = t.shape
+            if tuple(s.shape) != (n, hh, ww, c) or not s.is_contiguous():
+                raise ValueError(f"skip {tuple(s.shape)} does not match the ControlNet tap {tuple(t.shape)}")
+            wl = level_weights.get((hh, ww))
+            if wl is None or wl.dtype != torch.float32 or wl.numel() != n * hh * ww or not wl.is_contiguous() or wl.device != t.device:
+                raise ValueError(f"level_weights[{(hh, ww)}] must be a dense fp32 tensor of {n * hh * ww} values on {t.device}")
+        scratch = torch.empty(max(t.numel() for t, _, _, _ in jobs), dtype=torch.float32, device=x_mid.device)
+        for t, conv, s, m in jobs:
+            n, hh, ww, c = t.shape
+            rows = n * hh * ww
+            t32 = ops.igemm(t, conv, geom=(n, hh, ww), out_f32=True, out_scale=1.0, out=scratch[:rows * c].view(rows, c))
+            ops.weighted_residual_add(t32, level_weights[(hh, ww)].view(rows), ops.wview(s, rows, c), float(m) * conditioning_scale)
+            ops.drop_lo(s)
+
     @classmethod
     def from_unet(cls, unet, controlnet_conditioning_channel_order: str = "rgb",
                   conditioning_embedding_out_channels: Optional[Tuple[int, ...]] = (16, 32, 96, 256),

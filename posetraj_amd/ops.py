@@ -412,6 +412,33 @@ def axpy(a: torch.Tensor, r: torch.Tensor, m: float) -> torch.Tensor:
     return out
 
 
+def weighted_residual_add(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, scale: float = 1.0, rows: Optional[int] = None,
+                          cols: Optional[int] = None) -> torch.Tensor:
+    """``y[r, c] = fp16((scale * w[r]) * t[r, c] + (y[r, c] + y.lo[r, c]))`` IN PLACE on the fp16 ``y`` (``ptc_weighted_residual_add_f16``,
+    include/posetraj_control.h): ``t`` fp32 ``[rows, C]``, ``w`` fp32 ``[rows]``, both 2-D tensors may be pitched (``stride(0)``).  A
+    wide-stream ``y`` is read as its pair; the result is plain fp16, so the caller calls :func:`drop_lo` on the tensor ``y`` views.
+    ``rows`` / ``cols``: update only the leading rows / columns (default: all of ``y``)."""
+    _need(t, "t", torch.float32); _need(w, "w", torch.float32); _need(y, "y")
+    if t.dim() != 2 or y.dim() != 2 or t.stride(1) != 1 or y.stride(1) != 1:
+        raise RuntimeError(f"posetraj_amd.weighted_residual_add: `t` and `y` must be 2-D with unit column stride; got {tuple(t.shape)} / {tuple(y.shape)}")
+    rows = y.shape[0] if rows is None else int(rows)
+    cols = y.shape[1] if cols is None else int(cols)
+    if not (0 < rows <= min(y.shape[0], t.shape[0]) and 0 < cols <= min(y.shape[1], t.shape[1])):
+        raise RuntimeError(f"posetraj_amd.weighted_residual_add: {rows} x {cols} does not fit t {tuple(t.shape)} / y {tuple(y.shape)}")
+    if w.dim() != 1 or w.shape[0] < rows or w.stride(0) != 1 or w.device != y.device or t.device != y.device:
+        raise RuntimeError(f"posetraj_amd.weighted_residual_add: `w` must be a dense fp32 vector of at least {rows} rows on {y.device}; got {tuple(w.shape)}")
+    y_lo = getattr(y, "lo", None)
+    if y_lo is not None and (y_lo.shape != y.shape or y_lo.stride() != y.stride() or y_lo.device != y.device or y_lo.dtype != torch.float16):
+        raise RuntimeError("posetraj_amd.weighted_residual_add: the low half of `y` must share its shape, pitch, device and dtype")
+    if y_lo is not None and getattr(y, "lo_gen", 0) != _inplace_writes.get(y.data_ptr(), 0):
+        raise RuntimeError("posetraj_amd.weighted_residual_add: `y` was overwritten in place after its low half was produced (stale fp16 pair); "
+                           "call ops.drop_lo() on tensors whose high half is rewritten")
+    hip.checked().ptc_weighted_residual_add_f16(t.data_ptr(), t.stride(0), w.data_ptr(), float(scale), y.data_ptr(), _ptr(y_lo), y.stride(0),
+                                                rows, cols, _stream())
+    _inplace_writes[y.data_ptr()] = _inplace_writes.get(y.data_ptr(), 0) + 1
+    return y
+
+
 def silu(x: torch.Tensor) -> torch.Tensor:
     _need(x, "x")
     y = torch.empty_like(x)

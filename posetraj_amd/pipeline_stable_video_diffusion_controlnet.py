@@ -17,12 +17,13 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Callable, Dict, List, Optional, Union
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from . import ops
+from .control_schedule import check_control_weight, control_plan, is_scale_sequence, pool_control_weight, tap_sizes
 from .controlnet_sdv import ControlNetSDVModel
 from .modeling import BaseOutput
 from .scheduling_euler_discrete_karras_fix import PREDICTION_TYPES, EulerDiscreteScheduler
@@ -126,6 +127,7 @@ class StableVideoDiffusionPipelineControlNet:
         self._guidance_scale = None
         self._num_timesteps = 0
         self._graph_state = None                    # captured hipGraph of the per-iteration networks (denoise(use_graph=True))
+        self._control_graphs = {}                   # ... and of the other step kinds ("weighted" / "off") of the same geometry, by key
         self._side_stream = None                    # second HIP stream of denoise(overlap_streams=True)
 
     @classmethod
@@ -296,14 +298,36 @@ class StableVideoDiffusionPipelineControlNet:
     @torch.no_grad()
     def denoise(self, latents: torch.Tensor, image_latents: torch.Tensor, image_embeddings: torch.Tensor,
                 controlnet_condition: torch.Tensor, num_inference_steps: int = 25, min_guidance_scale: float = 1.0,
-                max_guidance_scale: float = 3.0, controlnet_cond_scale: float = 1.0,
+                max_guidance_scale: float = 3.0, controlnet_cond_scale: Union[float, Sequence[float]] = 1.0,
                 camera_cond: Optional[torch.Tensor] = None, callback_on_step_end: Optional[Callable] = None,
                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], use_graph: bool = False,
-                overlap_streams: bool = False, _networks=None) -> torch.Tensor:
+                overlap_streams: bool = False, _networks=None, control_guidance_start: float = 0.0,
+                control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``pipeline...:481-583``.  ``latents`` ``[Bc, F, 4, h, w]`` already scaled by ``init_noise_sigma``;
         ``image_latents`` ``[2*Bc, 4, h, w]`` (uncond halves first, one frame - it is repeated over frames, ``:466``);
         ``image_embeddings`` ``[2*Bc, 1, D]``; ``controlnet_condition`` ``[2*Bc, F, 3, H, W]`` in [-1, 1].
-        Returns the denoised latents in the dtype of ``latents``."""
+        Returns the denoised latents in the dtype of ``latents``.
+
+        Control strength beyond the reference (``posetraj_amd.control_schedule``; a call that gives none of these runs exactly the
+        launches it always ran):
+
+        ``control_guidance_start`` / ``control_guidance_end``: diffusers' window - with ``N`` steps, step ``i`` runs the ControlNet iff
+        ``not (i / N < start or (i + 1) / N > end)``; the other steps run the U-Net alone (no ControlNet launch at all).
+        ``controlnet_cond_scale``: one float, or ``num_inference_steps`` floats, one per step; a step whose scale is exactly 0.0 is
+        skipped like a step outside the window.
+        ``control_weight``: ``[F, h, w]`` or ``[Bc, F, h, w]`` at latent resolution, finite, intended range [0, 1]: multiplies every
+        ControlNet residual per frame and latent pixel (a tap of size ``(hh, ww)`` uses ``adaptive_avg_pool2d(control_weight, (hh, ww))``,
+        pooled once per call); both classifier-free-guidance halves of a clip get the same weights.  Per-frame strength ``s [F]`` is
+        the special case ``s[:, None, None].expand(F, h, w)``.
+        A ``control_weight`` or a per-step scale sends the ControlNet steps through ``ControlNetSDVModel._accumulate_into_weighted``,
+        whose factors live in device buffers: one captured graph serves every scale and every weight map."""
+        plan = control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
+        Bc_, F_, h_, w_ = latents.shape[0], latents.shape[1], latents.shape[3], latents.shape[4]
+        control_weight = check_control_weight(control_weight, Bc_, F_, h_, w_)
+        weighted = control_weight is not None or is_scale_sequence(controlnet_cond_scale)
+        scheduled = weighted or (float(control_guidance_start), float(control_guidance_end)) != (0.0, 1.0)
+        if scheduled and _networks is not None:
+            raise ValueError("`_networks` (another schedule of the two networks, A/B only) serves the plain loop: no control window, per-step scale or weight")
         if max_guidance_scale <= 1.0:
             # The reference's non-CFG branch (:438, :532) cannot run: latents / embeddings stay [Bc, ...] but the control
             # maps (:501-503) and added_time_ids (:521) are doubled unconditionally, so ControlNetSDVModel.forward reshapes
@@ -333,12 +357,28 @@ class StableVideoDiffusionPipelineControlNet:
         sig = self.scheduler._sigmas_host
         self._num_timesteps = len(timesteps)
         self.scheduler._step_index = None
-        def networks(sample, t, emb_, cond_, cam_):
+        # The three kinds of step (control_schedule): "plain" - the loop as the reference runs it, one scalar scale in the zero-convs'
+        # epilogues; "weighted" - the residuals times a per-(frame, pixel) factor read from device buffers (control_weight, per-step
+        # scales); "off" - outside the control window or scale 0: the U-Net alone.  Without the new arguments every step is plain.
+        kinds = ["plain"] * len(plan) if not scheduled else [("weighted" if weighted else "plain") if on else "off" for on, _ in plan]
+        step_scales = [s for _, s in plan]
+        level_base = None                    # weighted: {(hh, ww): fp32 [2 Bc F hh ww]} pooled weights, pooled once per call on the device
+        if "weighted" in kinds:
+            cw = torch.ones((Bc, F) + tuple(x.shape[3:]), dtype=torch.float32, device=dev) if control_weight is None else control_weight.to(dev)
+            level_base = pool_control_weight(cw, tap_sizes(x.shape[3], x.shape[4], len(self.controlnet.config.block_out_channels)))
+
+        def networks(sample, t, emb_, cond_, cam_, ids_, kind="plain", level_w=None):
             """ControlNet + U-Net of one iteration -> fp32 channels-last prediction [2Bc, F, h, w, 4].  The ControlNet
             residuals are accumulated straight into the U-Net's skips by the zero-convs' epilogues (no residual tensors,
-            no separate add passes); with ``overlap_streams`` the two encoders run concurrently."""
+            no separate add passes); with ``overlap_streams`` the two encoders run concurrently.  ``kind`` "weighted": through
+            ``_accumulate_into_weighted`` with the factors in ``level_w``; "off": no ControlNet, nothing to overlap or join."""
             if _networks is not None:        # tools/variants/split_cfg.py: another schedule of the same two networks (A/B only)
-                return _networks(self, sample, t, emb_, cond_, cam_, added_time_ids, controlnet_cond_scale)
+                return _networks(self, sample, t, emb_, cond_, cam_, ids_, controlnet_cond_scale)
+            if kind == "off":
+                enc = self.unet._encode(sample, t, emb_, ids_)
+                pred = self.unet._decode(enc, None, None, return_dict=False, residuals_added=True, out_f32=True)[0]
+                pred_cl = pred.permute(0, 1, 3, 4, 2)
+                return pred_cl if pred_cl.is_contiguous() else pred_cl.contiguous()
             main = torch.cuda.current_stream(dev)
             if overlap_streams:
                 # The U-Net's encoder half does not depend on the ControlNet (its outputs are added to the skips and to
@@ -350,10 +390,10 @@ class StableVideoDiffusionPipelineControlNet:
                 side = self._side_stream
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    enc = self.unet._encode(sample, t, emb_, added_time_ids)
+                    enc = self.unet._encode(sample, t, emb_, ids_)
             else:
-                enc = self.unet._encode(sample, t, emb_, added_time_ids)
-            taps, xm = self.controlnet._features(sample, t, emb_, added_time_ids, cond_,
+                enc = self.unet._encode(sample, t, emb_, ids_)
+            taps, xm = self.controlnet._features(sample, t, emb_, ids_, cond_,
                                                  cam_ if self.controlnet.config.camera else None)
             if overlap_streams:
                 main.wait_stream(side)
@@ -362,8 +402,12 @@ class StableVideoDiffusionPipelineControlNet:
                         tns.record_stream(main)               # allocated on the side stream, consumed on this one
                         if getattr(tns, "lo", None) is not None:
                             tns.lo.record_stream(main)        # ... and so is the low half of a wide-stream tensor
-            self.controlnet._accumulate_into(taps, xm, controlnet_cond_scale, enc["skips"],
-                                             self.unet._multiplicity(enc, len(taps)), enc["x"])
+            if kind == "weighted":           # the step's scale is folded into level_w before the launch (below): the scalar stays 1
+                self.controlnet._accumulate_into_weighted(taps, xm, 1.0, level_w, enc["skips"],
+                                                          self.unet._multiplicity(enc, len(taps)), enc["x"])
+            else:
+                self.controlnet._accumulate_into(taps, xm, controlnet_cond_scale, enc["skips"],
+                                                 self.unet._multiplicity(enc, len(taps)), enc["x"])
             pred = self.unet._decode(enc, None, None, return_dict=False, residuals_added=True, out_f32=True)[0]
             pred_cl = pred.permute(0, 1, 3, 4, 2)                                          # [2Bc, F, h, w, 4] contiguous
             return pred_cl if pred_cl.is_contiguous() else pred_cl.contiguous()
@@ -372,53 +416,106 @@ class StableVideoDiffusionPipelineControlNet:
         # replayed per iteration (and for later clips of the same geometry); the two fused loop kernels around them
         # carry the per-step scalars and stay eager.  The condition encoder is not in the graph: it runs once per clip
         # and refreshes its cached output in place.
-        gs = None
-        if use_graph:
-            key = (Bc, F, tuple(x.shape[3:]), tuple(cond.shape), None if cam is None else tuple(cam.shape),
-                   float(controlnet_cond_scale), id(self.unet), id(self.controlnet), self.unet._generation,
-                   self.controlnet._generation, bool(overlap_streams), getattr(_networks, '__name__', None), ops.dispatch_key())
-            gs = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
+        # One state per KIND of step: the plain one is ``self._graph_state`` under the key it always had (the scale is baked into its
+        # epilogues); "weighted" and "off" live in ``self._control_graphs`` under the same key with the kind in the scale's place -
+        # their launches do not depend on the scale: 25 distinct scales, or another weight map, replay one graph.  A state is found
+        # or captured at the first step of its kind in this call; later captures of a geometry share the first one's memory pool
+        # (the kinds replay one after the other on one stream and each prediction is consumed before the next replay), so the
+        # U-Net's activations are not held twice.
+        def graph_key(kind):
+            return (Bc, F, tuple(x.shape[3:]), tuple(cond.shape), None if cam is None else tuple(cam.shape),
+                    float(controlnet_cond_scale) if kind == "plain" else kind, id(self.unet), id(self.controlnet), self.unet._generation,
+                    self.controlnet._generation, bool(overlap_streams), getattr(_networks, '__name__', None), ops.dispatch_key())
+
+        same_geometry = lambda k1, k2: k1[:5] + k1[6:] == k2[:5] + k2[6:]
+        live = {}                            # kind -> the state this call uses: graph state (use_graph) or the eager step's buffers
+
+        def refresh_weights(st):
+            """This call's pooled weights into the buffers the state owns, in place (a captured graph reads those addresses)."""
+            if "wbase" not in st:
+                st["wbase"] = {sz: b.clone() for sz, b in level_base.items()}
+                st["wbuf"] = {sz: torch.empty_like(b) for sz, b in level_base.items()}
+            else:
+                for sz, b in level_base.items():
+                    st["wbase"][sz].copy_(b)
+            st["folded"] = None
+
+        def graph_state(kind, k, t):
+            key = graph_key(kind)
+            if kind == "plain":
+                gs = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
+            else:
+                gs = self._control_graphs.get(key)
+            on = kind != "off"               # an off step reads neither the control maps nor the camera
             if gs is None:
                 gs = dict(key=key, xin=torch.empty((2 * Bc, F, x.shape[3], x.shape[4], 8), dtype=torch.float16, device=dev),
-                          t=torch.zeros(1, dtype=torch.float32, device=dev), emb=emb.clone(), cond=cond.clone(),
-                          cam=None if cam is None else cam.clone(), ids=added_time_ids.clone())
+                          t=torch.zeros(1, dtype=torch.float32, device=dev), emb=emb.clone(), cond=cond.clone() if on else None,
+                          cam=None if cam is None or not on else cam.clone(), ids=added_time_ids.clone())
             else:
-                gs["emb"].copy_(emb); gs["cond"].copy_(cond); gs["ids"].copy_(added_time_ids)
-                if cam is not None:
-                    gs["cam"].copy_(cam)
-            added_time_ids = gs["ids"]
-            # once per clip: the condition encoder, eagerly (the in-place edits above bumped the tensors' versions),
-            # into a buffer this graph state owns: the captured graph reads that address whatever the ControlNet's
-            # cache holds after other (eager) calls
-            gs["cond_embed"] = self.controlnet._cond_embedding(gs["cond"], gs["cam"] if self.controlnet.config.camera else None,
-                                                              out=gs.get("cond_embed"))
+                gs["emb"].copy_(emb); gs["ids"].copy_(added_time_ids)
+                if on:
+                    gs["cond"].copy_(cond)
+                    if cam is not None:
+                        gs["cam"].copy_(cam)
+            if on:
+                # once per clip: the condition encoder, eagerly (the in-place edits above bumped the tensors' versions),
+                # into a buffer this graph state owns: the captured graph reads that address whatever the ControlNet's
+                # cache holds after other (eager) calls
+                gs["cond_embed"] = self.controlnet._cond_embedding(gs["cond"], gs["cam"] if self.controlnet.config.camera else None,
+                                                                  out=gs.get("cond_embed"))
+            if kind == "weighted":
+                refresh_weights(gs)
+                for sz, b in gs["wbase"].items():            # (the warm-up and the capture read defined values)
+                    gs["wbuf"][sz].copy_(b)
             if "graph" not in gs:
-                ops.scale_concat_input(x, il, sig[0], out=gs["xin"])
-                gs["t"].fill_(float(self.scheduler._timesteps_host[0]))
+                ops.scale_concat_input(x, il, sig[k], out=gs["xin"])
+                gs["t"].fill_(float(t))
+                run = lambda: networks(gs["xin"].permute(0, 1, 4, 2, 3), gs["t"], gs["emb"], gs["cond"], gs["cam"], gs["ids"], kind, gs.get("wbuf"))
                 warm = torch.cuda.Stream(device=dev)
                 warm.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(warm):                # warm-up: weight-only caches, allocator sizing
-                    networks(gs["xin"].permute(0, 1, 4, 2, 3), gs["t"], gs["emb"], gs["cond"], gs["cam"])
+                    run()
                 torch.cuda.current_stream(dev).wait_stream(warm)
+                others = [s_ for s_ in ([] if kind == "plain" else [self._graph_state]) + list(self._control_graphs.values())
+                          if s_ is not None and "graph" in s_ and same_geometry(s_["key"], key)]
                 g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_):
-                    gs["pred"] = networks(gs["xin"].permute(0, 1, 4, 2, 3), gs["t"], gs["emb"], gs["cond"], gs["cam"])
+                with torch.cuda.graph(g_, pool=others[0]["graph"].pool() if others else None):
+                    gs["pred"] = run()
                 gs["graph"] = g_
-                self._graph_state = gs
+                if kind == "plain":
+                    self._graph_state = gs
+                else:                                        # keep the dict small: the kinds of the current geometry only
+                    self._control_graphs = {k_: s_ for k_, s_ in self._control_graphs.items() if same_geometry(k_, key)}
+                    self._control_graphs[key] = gs
+            return gs
 
         for i in range(len(timesteps)):
             t = self.scheduler._timesteps_host[i]
             if self.scheduler._step_index is None:
                 self.scheduler._init_step_index(t)
             k = self.scheduler._step_index
-            if gs is not None:
-                ops.scale_concat_input(x, il, sig[k], out=gs["xin"])
-                gs["t"].fill_(float(t))
-                gs["graph"].replay()
-                pred_cl = gs["pred"]
+            kind = kinds[i]
+            st = live.get(kind)
+            if st is None:
+                if use_graph:
+                    st = graph_state(kind, k, t)
+                else:
+                    st = {}
+                    if kind == "weighted":
+                        refresh_weights(st)
+                live[kind] = st
+            if kind == "weighted" and st["folded"] != step_scales[i]:
+                for sz, b in st["wbase"].items():            # this step's scale, folded into the factors the kernels read
+                    torch.mul(b, step_scales[i], out=st["wbuf"][sz])
+                st["folded"] = step_scales[i]
+            if use_graph:
+                ops.scale_concat_input(x, il, sig[k], out=st["xin"])
+                st["t"].fill_(float(t))
+                st["graph"].replay()
+                pred_cl = st["pred"]
             else:
                 xin = ops.scale_concat_input(x, il, sig[k])                                # [2Bc, F, h, w, 8]
-                pred_cl = networks(xin.permute(0, 1, 4, 2, 3), t, emb, cond, cam)          # [2Bc, F, 8, h, w] view
+                pred_cl = networks(xin.permute(0, 1, 4, 2, 3), t, emb, cond, cam, added_time_ids, kind, st.get("wbuf"))   # [2Bc, F, 8, h, w] view
             ops.cfg_euler_step(pred_cl, guidance, sig[k], sig[k + 1], ptype, x)
             self.scheduler._step_index += 1
             self.scheduler.is_scale_input_called = True
@@ -442,14 +539,23 @@ class StableVideoDiffusionPipelineControlNet:
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], return_dict: bool = True,
                  controlnet_cond_scale=1.0, batch_size=1, camera_cond=None,
                  image_embeddings: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
-                 use_graph: bool = True, overlap_streams: bool = True):
+                 use_graph: bool = True, overlap_streams: bool = True, control_guidance_start: float = 0.0,
+                 control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None):
         """Same signature as the reference (``pipeline...:316-340``; ``camera_cond`` from the ``_cam`` twin) plus
         ``image_embeddings`` ``[2,1,D]`` / ``image_latents`` ``[2,4,h,w]`` (the outputs of the CLIP / VAE-encode stages,
         ``:441,457``, for callers that have them already) and ``use_graph`` / ``overlap_streams`` (the loop as a replayed
         hipGraph with the ControlNet and the U-Net encoder on two streams - the configuration ``bench.py`` measures;
         bit-identical to eager launches, ``tests/test_model_gpu.py``).  ``fps``, ``motion_bucket_id`` and
-        ``noise_aug_strength`` do not reach the U-Net in the reference either (Q4)."""
+        ``noise_aug_strength`` do not reach the U-Net in the reference either (Q4).
+
+        Beyond the reference (see ``denoise``): ``control_guidance_start`` / ``control_guidance_end`` (diffusers' control window over
+        the steps), ``controlnet_cond_scale`` as one float per step, and ``control_weight`` ``[F, h, w]`` / ``[Bc, F, h, w]`` at latent
+        resolution (``h = height // 8``), intended range [0, 1] - a weight per frame and latent pixel on every ControlNet residual;
+        per-frame strength ``s [F]`` is ``s[:, None, None].expand(F, h, w)``.  They are checked before any stage runs."""
         num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
+        control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
+        check_control_weight(control_weight, batch_size * num_videos_per_prompt, num_frames, height // self.vae_scale_factor,
+                             width // self.vae_scale_factor)
         decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames                # :422
         self.check_inputs(image, height, width)
         if output_type != "latent" and self.vae is None:
@@ -493,7 +599,9 @@ class StableVideoDiffusionPipelineControlNet:
             cam = torch.cat([cam] * 2)
         latents = self.denoise(lat, image_latents, image_embeddings, cond, num_inference_steps, min_guidance_scale,
                                max_guidance_scale, controlnet_cond_scale, cam, callback_on_step_end,
-                               callback_on_step_end_tensor_inputs, use_graph=use_graph, overlap_streams=overlap_streams)
+                               callback_on_step_end_tensor_inputs, use_graph=use_graph, overlap_streams=overlap_streams,
+                               control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
+                               control_weight=control_weight)
         if not output_type == "latent":                                                     # :585-592
             if needs_upcasting:
                 self.vae.to(dtype=torch.float16)

@@ -22,7 +22,18 @@ ap.add_argument("--image"); ap.add_argument("--tracks"); ap.add_argument("--out"
 ap.add_argument("--svd-dir"); ap.add_argument("--controlnet-dir")
 ap.add_argument("--height", type=int, default=320); ap.add_argument("--width", type=int, default=576)
 ap.add_argument("--steps", type=int, default=25)
+ap.add_argument("--control-start", type=float, default=0.0, help="control_guidance_start: fraction of the steps before the ControlNet starts")
+ap.add_argument("--control-end", type=float, default=1.0, help="control_guidance_end: fraction of the steps after which the ControlNet is skipped")
+ap.add_argument("--control-region", help="x0,y0,x1,y1: a box in LATENT pixels (image pixels / 8, x1 / y1 exclusive); the control applies inside it only")
 a = ap.parse_args()
+control_weight = None
+if a.control_region:                                                 # box -> [F, h, w] weight map: 1 inside, 0 outside, every frame
+    x0, y0, x1, y1 = (int(v) for v in a.control_region.split(","))
+    h, w = a.height // 8, a.width // 8
+    if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):
+        ap.error(f"--control-region {a.control_region}: need 0 <= x0 < x1 <= {w} and 0 <= y0 < y1 <= {h} (latent pixels)")
+    control_weight = torch.zeros(14, h, w)
+    control_weight[:, y0:y1, x0:x1] = 1.0
 dev = torch.device("cuda:0")
 if a.svd_dir and a.controlnet_dir:                                   # scripts/...:335-339
     controlnet = ControlNetSDVModel.from_pretrained(a.controlnet_dir, subfolder="controlnet", device=dev)
@@ -43,7 +54,8 @@ tracks = load_tracks(a.tracks) if a.tracks else bench.synth_tracks(14, original_
 maps = trajectory_maps(tracks, [a.height, a.width], original_size, num_frames=14, device=dev)        # :426-447 without cv2
 t0 = time.time()
 frames = pipe(image, maps, decode_chunk_size=8, num_frames=14, motion_bucket_id=10, controlnet_cond_scale=1.0, width=a.width,
-              height=a.height, num_inference_steps=a.steps).frames   # :451
+              height=a.height, num_inference_steps=a.steps, control_guidance_start=a.control_start, control_guidance_end=a.control_end,
+              control_weight=control_weight).frames                  # :451 (+ the control window / region, beyond the reference)
 torch.cuda.synchronize()
 print(f"{len(frames[0])} frames of {frames[0][0].size} in {time.time() - t0:.2f} s (first call: includes the hipGraph capture)")
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
