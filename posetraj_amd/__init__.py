@@ -24,6 +24,7 @@ from .controlnet_sdv import ControlNetOutput, ControlNetSDVModel
 from .pipeline_stable_video_diffusion_controlnet import (StableVideoDiffusionControlNetPipeline,
                                                          StableVideoDiffusionPipelineControlNet,
                                                          StableVideoDiffusionPipelineOutput)
+from .scheduling_dpmpp_2m import DPMPP2MDiscreteScheduler
 from .training import ControlNetTrainer, controlnet_training_loss
 from .scheduling_euler_discrete_karras_fix import (SVD_SCHEDULER_CONFIG, EulerDiscreteScheduler,
                                                    EulerDiscreteSchedulerOutput)
@@ -31,7 +32,7 @@ from .unet_spatio_temporal_condition_controlnet import (UNetSpatioTemporalCondit
                                                         UNetSpatioTemporalConditionOutput)
 
 __all__ = ["AutoencoderKLTemporalDecoder", "CLIPVisionModelWithProjection", "ControlNetOutput", "ControlNetSDVModel", "ControlNetTrainer",
-           "controlnet_training_loss", "StableVideoDiffusionControlNetPipeline",
+           "controlnet_training_loss", "DPMPP2MDiscreteScheduler", "StableVideoDiffusionControlNetPipeline",
            "StableVideoDiffusionPipelineControlNet", "StableVideoDiffusionPipelineOutput", "SVD_SCHEDULER_CONFIG",
            "EulerDiscreteScheduler", "EulerDiscreteSchedulerOutput", "UNetSpatioTemporalConditionControlNetModel",
            "UNetSpatioTemporalConditionOutput"]

@@ -13,7 +13,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.abspath(os.environ["PT_LIB"]) if os.environ.get("PT_LIB") else os.path.join(HERE, "libposetraj_hip.so")   # PT_LIB: A/B against another build on one box
-SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip", "batch.hip", "control.hip"]
+SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip", "batch.hip", "control.hip", "sampler.hip"]
 HEADERS = ["pt_common.h", "igemm_tail.h", "pt_fold.h"]
 HEADER = os.path.join(HERE, "..", "include", "posetraj_hip.h")
 STRUCT_CLASSES = {"pt_igemm_params": "IgemmParams", "pt_ffn_params": "FfnParams", "pt_lnlin_params": "LnLinParams",
@@ -29,6 +29,8 @@ TEMPORAL_HEADER = os.path.join(HERE, "..", "include", "posetraj_temporal.h")
 BATCH_HEADER = os.path.join(HERE, "..", "include", "posetraj_batch.h")
 # the control-weight extension (include/posetraj_control.h: entry points `ptc_*`, a version of its own): per-row weighted accumulation of the ControlNet residuals
 CONTROL_HEADER = os.path.join(HERE, "..", "include", "posetraj_control.h")
+# the sampler extension (include/posetraj_sampler.h: entry points `pts_*`, a version of its own): the linear multistep (DPM-Solver++(2M)) step
+SAMPLER_HEADER = os.path.join(HERE, "..", "include", "posetraj_sampler.h")
 
 _lib = _checked = None
 
@@ -39,7 +41,7 @@ _lib = _checked = None
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _TYPE = r"(?:const\s+)?\w+\s*\*?"
 _DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
-                            | (?P<ret>%s)\s*\b(?P<fn>pt[odtbc]?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
+                            | (?P<ret>%s)\s*\b(?P<fn>pt[odtbcs]?_[a-z0-9_]+)\s*\((?P<params>[^()]*)\)\s*;
                             | extern\s+"C"\s*\{ | \} )""" % _TYPE, re.X)
 _FIELD = re.compile(r"(%s)\s*\b(\w+(?:\s*,\s*\w+)*)" % _TYPE)         # `int32_t C0, C1`, `const void* x0`; a parameter is the one-name case
 
@@ -95,7 +97,7 @@ def _parse_header(text: str, struct_classes: dict = STRUCT_CLASSES, version_macr
             params = m.group("params").strip()
             protos[m.group("fn")] = (" ".join(m.group("ret").split()), [] if params == "void" else [t for t, _ in _declarators(params, ",")])
         pos = m.end()
-    named = re.findall(r"pt[odtbc]?_[a-z0-9_]+\s*\(", text)
+    named = re.findall(r"pt[odtbcs]?_[a-z0-9_]+\s*\(", text)
     if len(named) != len(protos):
         raise ValueError(f"posetraj_hip.h: {len(named)} names are followed by '(' but {len(protos)} prototypes were read")
     return int(version.group(1)), {k: v for k, v in structs.items() if k not in (known_structs or {})}, protos
@@ -123,6 +125,9 @@ BATCH_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STR
 with open(CONTROL_HEADER) as _f:
     CONTROL_ABI_VERSION, _, CONTROL_PROTOTYPES = _parse_header(_f.read(), {}, "PT_CONTROL_ABI_VERSION", _STRUCTS)
 CONTROL_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in CONTROL_PROTOTYPES.items()}
+with open(SAMPLER_HEADER) as _f:
+    SAMPLER_ABI_VERSION, _, SAMPLER_PROTOTYPES = _parse_header(_f.read(), {}, "PT_SAMPLER_ABI_VERSION", _STRUCTS)
+SAMPLER_SIGNATURES = {name: (_ctype(ret, _STRUCTS, returned=True), [_ctype(t, _STRUCTS) for t in params]) for name, (ret, params) in SAMPLER_PROTOTYPES.items()}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -133,7 +138,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER, CONTROL_HEADER]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER, CONTROL_HEADER, SAMPLER_HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -210,7 +215,7 @@ def source_digest() -> str:
     to replay them for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER, CONTROL_HEADER]):
+    for path in sorted([os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [HEADER, OPTIM_HEADER, DET_HEADER, TEMPORAL_HEADER, BATCH_HEADER, CONTROL_HEADER, SAMPLER_HEADER]):
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
     return h.hexdigest()
@@ -225,18 +230,20 @@ def _load(errcheck=None):
                            "(posetraj_amd has no CPU or PyTorch fallback path)")
     L = C.CDLL(LIB_PATH)
     for sigs, protos in ((SIGNATURES, PROTOTYPES), (OPTIM_SIGNATURES, OPTIM_PROTOTYPES), (DET_SIGNATURES, DET_PROTOTYPES),
-                         (TEMPORAL_SIGNATURES, TEMPORAL_PROTOTYPES), (BATCH_SIGNATURES, BATCH_PROTOTYPES), (CONTROL_SIGNATURES, CONTROL_PROTOTYPES)):
+                         (TEMPORAL_SIGNATURES, TEMPORAL_PROTOTYPES), (BATCH_SIGNATURES, BATCH_PROTOTYPES), (CONTROL_SIGNATURES, CONTROL_PROTOTYPES),
+                         (SAMPLER_SIGNATURES, SAMPLER_PROTOTYPES)):
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)            # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
-            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version", "ptd_abi_version", "ptt_abi_version", "ptb_abi_version", "ptc_abi_version"):
+            if errcheck is not None and protos[name][0] == "int" and name not in ("pt_abi_version", "pto_abi_version", "ptd_abi_version", "ptt_abi_version", "ptb_abi_version", "ptc_abi_version", "pts_abi_version"):
                 fn.errcheck = errcheck
     if (L.pt_abi_version() != ABI_VERSION or L.pto_abi_version() != OPTIM_ABI_VERSION or L.ptd_abi_version() != DET_ABI_VERSION
-            or L.ptt_abi_version() != TEMPORAL_ABI_VERSION or L.ptb_abi_version() != BATCH_ABI_VERSION or L.ptc_abi_version() != CONTROL_ABI_VERSION):
+            or L.ptt_abi_version() != TEMPORAL_ABI_VERSION or L.ptb_abi_version() != BATCH_ABI_VERSION or L.ptc_abi_version() != CONTROL_ABI_VERSION
+            or L.pts_abi_version() != SAMPLER_ABI_VERSION):
         raise RuntimeError(f"libposetraj_hip.so ABI {L.pt_abi_version()} / optimizer extension {L.pto_abi_version()} / deterministic extension "
                            f"{L.ptd_abi_version()} / long-clip extension {L.ptt_abi_version()} / clip-batch extension {L.ptb_abi_version()} / control-weight extension "
-                           f"{L.ptc_abi_version()} != expected {ABI_VERSION} / {OPTIM_ABI_VERSION} / {DET_ABI_VERSION} / {TEMPORAL_ABI_VERSION} / {BATCH_ABI_VERSION} / "
-                           f"{CONTROL_ABI_VERSION}; rebuild")
+                           f"{L.ptc_abi_version()} / sampler extension {L.pts_abi_version()} != expected {ABI_VERSION} / {OPTIM_ABI_VERSION} / {DET_ABI_VERSION} / "
+                           f"{TEMPORAL_ABI_VERSION} / {BATCH_ABI_VERSION} / {CONTROL_ABI_VERSION} / {SAMPLER_ABI_VERSION}; rebuild")
     return L
 
 

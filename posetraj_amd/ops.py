@@ -537,6 +537,39 @@ def euler_step(model_output: torch.Tensor, sample_f32: torch.Tensor, sigma: floa
     return out
 
 
+def cfg_multistep_step(noise_pred: torch.Tensor, guidance: torch.Tensor, coefs, latents: torch.Tensor, denoised_prev: torch.Tensor) -> None:
+    """Classifier-free guidance + one linear multistep update (``pts_cfg_multistep_step``, include/posetraj_sampler.h), IN PLACE on
+    fp32 ``latents`` and ``denoised_prev`` ``[Bc, F, 4, h, w]``; ``noise_pred`` fp16 or fp32 channels-last ``[2Bc, F, h, w, ld]``.
+    ``coefs``: ``(c_skip, c_out, a, b, c)`` of the step (``DPMPP2MDiscreteScheduler.coefficients``); with ``c == 0`` ``denoised_prev``
+    is written but not read."""
+    f32 = noise_pred.dtype == torch.float32
+    _need(noise_pred, "noise_pred", noise_pred.dtype if f32 else torch.float16)
+    _need(latents, "latents", torch.float32); _need(guidance, "guidance", torch.float32); _need(denoised_prev, "denoised_prev", torch.float32)
+    if denoised_prev.shape != latents.shape or not (latents.is_contiguous() and denoised_prev.is_contiguous()):
+        raise RuntimeError(f"posetraj_amd.cfg_multistep_step: latents {tuple(latents.shape)} / denoised_prev {tuple(denoised_prev.shape)} must be contiguous and alike")
+    Bc, F, _, h, w = latents.shape
+    c_skip, c_out, a, b, c = (float(v) for v in coefs)
+    hip.checked().pts_cfg_multistep_step(noise_pred.data_ptr(), 1 if f32 else 0, noise_pred.stride(-2), guidance.data_ptr(), c_skip, c_out, a, b, c,
+                                         Bc, F, h, w, latents.data_ptr(), denoised_prev.data_ptr(), _stream())
+
+
+def multistep_step(model_output: torch.Tensor, sample_f32: torch.Tensor, coefs, denoised_prev: torch.Tensor) -> torch.Tensor:
+    """One linear multistep update on flat tensors (``pts_multistep_step``): returns the new fp32 sample; ``denoised_prev`` (fp32,
+    the sample's shape, contiguous) is updated in place and not read when ``c == 0``.  ``coefs`` as in ``cfg_multistep_step``."""
+    if not model_output.is_cuda or model_output.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("posetraj_amd.multistep_step: needs a fp16/fp32 model_output on the GPU (no CPU path exists)")
+    _need(sample_f32, "sample", torch.float32); _need(denoised_prev, "denoised_prev", torch.float32)
+    if not (model_output.shape == sample_f32.shape == denoised_prev.shape) or not denoised_prev.is_contiguous():
+        raise RuntimeError(f"posetraj_amd.multistep_step: shapes {tuple(model_output.shape)} / {tuple(sample_f32.shape)} / {tuple(denoised_prev.shape)}")
+    mo = model_output.contiguous()
+    x = sample_f32.contiguous()
+    out = torch.empty_like(x)
+    c_skip, c_out, a, b, c = (float(v) for v in coefs)
+    hip.checked().pts_multistep_step(mo.data_ptr(), 1 if mo.dtype == torch.float32 else 0, x.data_ptr(), c_skip, c_out, a, b, c,
+                                     denoised_prev.data_ptr(), out.data_ptr(), x.numel(), _stream())
+    return out
+
+
 def add_noise(x: torch.Tensor, noise: torch.Tensor, sigma_per_sample: torch.Tensor) -> torch.Tensor:
     """``x + noise * sigma[b]`` in the dtype of ``x`` (fp16 / fp32); ``sigma_per_sample`` fp32 ``[batch]`` on the device."""
     if not x.is_cuda or x.dtype not in (torch.float16, torch.float32):

@@ -489,6 +489,11 @@ class StableVideoDiffusionPipelineControlNet:
                     self._control_graphs[key] = gs
             return gs
 
+        # The sampler: a scheduler of order 2 (DPMPP2MDiscreteScheduler) takes the multistep kernel with its own host-computed
+        # coefficients and one more latent-sized tensor, the previous denoised estimate; any other takes the Euler kernel.  Both run
+        # after the networks, outside the captured graphs: one graph serves both schedulers.
+        multistep = getattr(self.scheduler, "order", 1) == 2
+        d_prev = torch.empty_like(x) if multistep else None
         for i in range(len(timesteps)):
             t = self.scheduler._timesteps_host[i]
             if self.scheduler._step_index is None:
@@ -516,7 +521,10 @@ class StableVideoDiffusionPipelineControlNet:
             else:
                 xin = ops.scale_concat_input(x, il, sig[k])                                # [2Bc, F, h, w, 8]
                 pred_cl = networks(xin.permute(0, 1, 4, 2, 3), t, emb, cond, cam, added_time_ids, kind, st.get("wbuf"))   # [2Bc, F, 8, h, w] view
-            ops.cfg_euler_step(pred_cl, guidance, sig[k], sig[k + 1], ptype, x)
+            if multistep:                    # DPM-Solver++(2M): this call's first step has no previous estimate (c = 0: d_prev is written, not read)
+                ops.cfg_multistep_step(pred_cl, guidance, self.scheduler.coefficients(k, first=i == 0), x, d_prev)
+            else:
+                ops.cfg_euler_step(pred_cl, guidance, sig[k], sig[k + 1], ptype, x)
             self.scheduler._step_index += 1
             self.scheduler.is_scale_input_called = True
             if callback_on_step_end is not None:

@@ -4,7 +4,8 @@ load (or random-init) the models, build the 13 + 1 trajectory maps from a tracks
 script does, save the frames as a GIF.
 
     python tools/run_inference_example.py --image first_frame.png --tracks tracks.json --out out.gif \\
-        [--svd-dir <stable-video-diffusion-img2vid dir> --controlnet-dir <dir with controlnet/>] [--height 320 --width 576]
+        [--svd-dir <stable-video-diffusion-img2vid dir> --controlnet-dir <dir with controlnet/>] [--height 320 --width 576] \\
+        [--sampler dpmpp2m --steps 15]
 Without checkpoint directories the models are random-init at full SVD size (the output is then noise - a smoke run of the whole
 image-to-video path on the MI355X)."""
 import argparse, json, os, sys, time
@@ -13,7 +14,7 @@ import numpy as np
 import PIL.Image
 import torch
 import bench
-from posetraj_amd import (AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, ControlNetSDVModel, EulerDiscreteScheduler,
+from posetraj_amd import (AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, ControlNetSDVModel, DPMPP2MDiscreteScheduler, EulerDiscreteScheduler,
                           SVD_SCHEDULER_CONFIG, StableVideoDiffusionPipelineControlNet, UNetSpatioTemporalConditionControlNetModel)
 from posetraj_amd.trajectory import load_tracks, trajectory_maps
 
@@ -22,6 +23,7 @@ ap.add_argument("--image"); ap.add_argument("--tracks"); ap.add_argument("--out"
 ap.add_argument("--svd-dir"); ap.add_argument("--controlnet-dir")
 ap.add_argument("--height", type=int, default=320); ap.add_argument("--width", type=int, default=576)
 ap.add_argument("--steps", type=int, default=25)
+ap.add_argument("--sampler", default="euler", choices=["euler", "dpmpp2m"], help="dpmpp2m: DPM-Solver++(2M), second order, meant for fewer --steps (beyond the reference)")
 ap.add_argument("--control-start", type=float, default=0.0, help="control_guidance_start: fraction of the steps before the ControlNet starts")
 ap.add_argument("--control-end", type=float, default=1.0, help="control_guidance_end: fraction of the steps after which the ControlNet is skipped")
 ap.add_argument("--control-region", help="x0,y0,x1,y1: a box in LATENT pixels (image pixels / 8, x1 / y1 exclusive); the control applies inside it only")
@@ -45,6 +47,8 @@ else:
     pipe = StableVideoDiffusionPipelineControlNet(vae=AutoencoderKLTemporalDecoder(**bench.SVD_VAE).init_random_(seed=3, device=dev),
                                                   image_encoder=CLIPVisionModelWithProjection(**bench.CLIP_VIT_H).init_random_(seed=4, device=dev),
                                                   unet=unet, controlnet=controlnet, scheduler=EulerDiscreteScheduler(**SVD_SCHEDULER_CONFIG))
+if a.sampler == "dpmpp2m":                                           # the swap: same tables, same config, another update rule
+    pipe.scheduler = DPMPP2MDiscreteScheduler.from_config(pipe.scheduler.config)
 if a.image:
     image = PIL.Image.open(a.image).convert("RGB")
 else:
