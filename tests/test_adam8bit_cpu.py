@@ -90,52 +90,18 @@ def test_full_width_controlnet_state_is_a_quarter_of_the_fp32_moments():
     assert plan["n_work"] < 2 ** 31 and max(s[5] for s in plan["segments"]) < 2 ** 31
 
 
-def test_extension_header_bindings_structs_and_symbols(tmp_path):
-    """include/posetraj_optim.h the way tests/test_host_cpu.py treats include/posetraj_hip.h: a C++ compiler confirms the struct and
-    the prototypes the parser read, the library defines every declared ``pto_`` symbol and no other, the product passes as many
-    arguments as declared - and the main header's ABI is what it was."""
-    import ast, re, shutil, subprocess
+def test_segment_struct_and_the_host_refusal_of_the_step():
+    """The table entry the kernel reads, as ``hip`` binds it from include/posetraj_optim.h (the header's contract with the library:
+    tests/test_abi_cpu.py), and the step's refusal of null pointers before any launch."""
     from posetraj_amd import hip
     hip.build()
     assert [f[0] for f in hip.Adam8Segment._fields_] == ["start", "count", "state", "kind", "work"] and ctypes.sizeof(hip.Adam8Segment) == 32
+    assert hip.ABIS["optim"].structs == {"pt_adam8_segment": hip.Adam8Segment}
     seg = hip.Adam8Segment(8, 320, 16, 1, 3)
     assert (seg.start, seg.count, seg.state, seg.kind, seg.work) == (8, 320, 16, 1, 3)
-    assert hip.OPTIM_ABI_VERSION == 1 and set(hip.OPTIM_SIGNATURES) == {"pto_abi_version", "pto_adamw8_f32", "pto_adam8_dequant_f32"}
-    assert not set(hip.OPTIM_SIGNATURES) & set(hip.SIGNATURES) and hip.ABI_VERSION == 10
-    hdr = open(hip.OPTIM_HEADER).read()
-    assert set(re.findall(r"\b(pto_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))) == set(hip.OPTIM_SIGNATURES)
-    tu = ["#include <cstddef>", "#include <type_traits>", '#include "posetraj_hip.h"', '#include "posetraj_optim.h"']
-    cls = hip.Adam8Segment
-    tu.append(f"static_assert(sizeof(pt_adam8_segment) == {ctypes.sizeof(cls)}, \"sizeof\");")
-    for field, typ in cls._fields_:
-        tu.append(f"static_assert(offsetof(pt_adam8_segment, {field}) == {getattr(cls, field).offset} && sizeof(pt_adam8_segment::{field}) == {ctypes.sizeof(typ)}, \"{field}\");")
-    for fn, (ret, params) in hip.OPTIM_PROTOTYPES.items():
-        assert len(hip.OPTIM_SIGNATURES[fn][1]) == len(params)
-        tu.append(f"static_assert(std::is_same_v<decltype(&{fn}), {ret} (*)({', '.join(params)})>, \"{fn}\");")
-    tu.append(f"static_assert(PT_OPTIM_ABI_VERSION == {hip.OPTIM_ABI_VERSION} && PT_ABI_VERSION == {hip.ABI_VERSION}, \"versions\");")
-    src = tmp_path / "optim_abi_probe.cpp"
-    src.write_text("\n".join(tu) + "\n")
-    cxx = shutil.which("c++") or shutil.which("clang++") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    r = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(os.path.dirname(hip.HEADER)), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("pto_")}
-    assert defined == set(hip.OPTIM_SIGNATURES), defined ^ set(hip.OPTIM_SIGNATURES)
-    L, C = hip.lib(), hip.checked()
-    assert L.pto_abi_version() == C.pto_abi_version() == 1
-    assert C.pto_adamw8_f32.errcheck is hip._raise_on_status and not C.pto_abi_version.errcheck and not L.pto_adamw8_f32.errcheck
+    L = hip.lib()
     assert L.pto_adamw8_f32(*([None] * 11), 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 1, 1.0, None, 0, None, 0.0, None) != 0      # refused on the host: no launch
     assert b"pto_adamw8_f32" in L.pt_last_error()
-    sites = 0
-    pkg = os.path.dirname(hip.__file__)
-    for f in sorted(os.listdir(pkg)):
-        if f.endswith(".py"):
-            for node in ast.walk(ast.parse(open(os.path.join(pkg, f)).read())):
-                if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ("pto_adamw8_f32", "pto_adam8_dequant_f32"):
-                    sites += 1
-                    assert not node.keywords and not any(isinstance(a, ast.Starred) for a in node.args)
-                    assert len(node.args) == len(hip.OPTIM_SIGNATURES[node.func.attr][1]), (f, node.lineno)
-    assert sites == 2
 
 
 def test_checkpoint_of_the_8bit_state_round_trips_and_the_kinds_do_not_mix(tmp_path):

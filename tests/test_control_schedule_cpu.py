@@ -2,15 +2,11 @@
 rule, the validation of the three arguments, the pooling of a weight map to the ControlNet's tap sizes, and the control-weight
 extension of the C ABI (include/posetraj_control.h) as ``posetraj_amd.hip`` reads it.  No device."""
 import inspect
-import re
-import subprocess
 
 import pytest
 import torch
 
 from posetraj_amd import control_schedule as CS
-
-ENTRIES = {"ptc_abi_version", "ptc_weighted_residual_add_f16"}
 
 
 def keep(n, start, end):
@@ -142,26 +138,14 @@ def test_denoise_signature_and_defaults():
     assert all(word in CamPipe.__call__.__doc__ for word in ("control_guidance_start", "control_guidance_end", "control_weight"))
 
 
-def test_control_extension_header_bindings_and_exports():
-    """The header is read like the other extensions, declares its version macro, the library defines every declared ``ptc_`` symbol and
-    no other, the build and the source digest know the header and the source, and the host refuses bad arguments before any launch."""
+def test_control_entry_point_prototype_and_host_refusals():
+    """The exact prototype ``hip`` read from include/posetraj_control.h (the header's contract with the library: tests/test_abi_cpu.py),
+    and the host refuses bad arguments before any launch."""
     from posetraj_amd import hip
-    text = open(hip.CONTROL_HEADER).read()
-    assert re.search(r"^#define\s+PT_CONTROL_ABI_VERSION\s+1\s*$", text, flags=re.M)
-    version, structs, protos = hip._parse_header(text, {}, "PT_CONTROL_ABI_VERSION", hip._STRUCTS)
-    assert version == hip.CONTROL_ABI_VERSION == 1 and not structs and set(protos) == set(hip.CONTROL_SIGNATURES) == ENTRIES
-    assert protos["ptc_weighted_residual_add_f16"] == ("int", ["const float*", "int64_t", "const float*", "float", "void*", "const void*", "int64_t",
-                                                               "int64_t", "int32_t", "void*"])
-    assert not set(hip.CONTROL_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.OPTIM_SIGNATURES) | set(hip.DET_SIGNATURES) |
-                                              set(hip.TEMPORAL_SIGNATURES) | set(hip.BATCH_SIGNATURES))
-    hdr = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    assert set(re.findall(r"\b(ptc_[a-z0-9_]+)\s*\(", hdr)) == ENTRIES
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ptc_")} == ENTRIES
-    assert "control.hip" in hip.SOURCES and "CONTROL_HEADER" in inspect.getsource(hip.build) and "CONTROL_HEADER" in inspect.getsource(hip.source_digest)
+    assert hip.ABIS["control"].prototypes["ptc_weighted_residual_add_f16"] == (
+        "int", ["const float*", "int64_t", "const float*", "float", "void*", "const void*", "int64_t", "int64_t", "int32_t", "void*"])
+    assert "control.hip" in hip.SOURCES
     L, C = hip.lib(), hip.checked()
-    assert L.ptc_abi_version() == C.ptc_abi_version() == 1
-    assert C.ptc_weighted_residual_add_f16.errcheck is hip._raise_on_status and not C.ptc_abi_version.errcheck and not L.ptc_weighted_residual_add_f16.errcheck
     assert L.ptc_weighted_residual_add_f16(None, 64, None, 1.0, None, None, 64, 8, 64, None) != 0 and b"null pointer" in L.pt_last_error()
     assert L.ptc_weighted_residual_add_f16(256, 64, 256, 1.0, 256, None, 64, 8, 12, None) != 0 and b"ptc_weighted_residual_add_f16" in L.pt_last_error()
     assert L.ptc_weighted_residual_add_f16(256, 60, 256, 1.0, 256, None, 64, 8, 64, None) != 0 and b"pitch" in L.pt_last_error()

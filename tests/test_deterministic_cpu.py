@@ -1,19 +1,11 @@
-"""``ControlNetTrainer(deterministic=True)`` on the host: the extension header include/posetraj_det.h and its bindings, the product's
+"""``ControlNetTrainer(deterministic=True)`` on the host: the bindings of include/posetraj_det.h the product relies on, the product's
 call sites, the refusals that need no launch.  No kernel runs here (tests/test_deterministic_gpu.py)."""
 import ast
 import ctypes
 import inspect
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
-
-ENTRIES = {"ptd_abi_version", "ptd_groupnorm_bwd_ws_floats", "ptd_groupnorm_bwd", "ptd_layernorm_bwd_ws_floats", "ptd_layernorm_bwd",
-           "ptd_colsum_ws_floats", "ptd_colsum_f16", "ptd_dot_diff_ws_floats", "ptd_dot_diff", "ptd_dot_diff_dev", "ptd_sumsq_ws_floats",
-           "ptd_sumsq_f32", "ptd_gemm_ws_floats", "ptd_gemm_f16"}
-
 
 @pytest.fixture(scope="module")
 def hip():
@@ -22,35 +14,12 @@ def hip():
     return hip
 
 
-def test_extension_header_bindings_and_symbols(hip, tmp_path):
-    """include/posetraj_det.h the way tests/test_adam8bit_cpu.py treats the optimizer header: a C++ compiler confirms the prototypes the
-    parser read, the library defines every declared ``ptd_`` symbol and no other - and the two older headers are what they were."""
-    assert hip.DET_ABI_VERSION == 1 and set(hip.DET_SIGNATURES) == ENTRIES
-    assert not set(hip.DET_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.OPTIM_SIGNATURES))
-    assert all(n.startswith("ptd_") and not n.startswith(("pt_", "pto_")) for n in hip.DET_SIGNATURES)
-    assert hip.ABI_VERSION == 10 and len(hip.SIGNATURES) == 76 and hip.OPTIM_ABI_VERSION == 1 and len(hip.OPTIM_SIGNATURES) == 3
-    hdr = re.sub(r"/\*.*?\*/", " ", open(hip.DET_HEADER).read(), flags=re.S)
-    assert set(re.findall(r"\b(ptd_[a-z0-9_]+)\s*\(", hdr)) == ENTRIES
-    tu = ["#include <type_traits>", '#include "posetraj_det.h"']
-    for fn, (ret, params) in hip.DET_PROTOTYPES.items():
-        assert len(hip.DET_SIGNATURES[fn][1]) == len(params)
-        tu.append(f"static_assert(std::is_same_v<decltype(&{fn}), {ret} (*)({', '.join(params) or 'void'})>, \"{fn}\");")
-    tu.append(f"static_assert(PT_DET_ABI_VERSION == {hip.DET_ABI_VERSION} && PT_ABI_VERSION == {hip.ABI_VERSION}, \"versions\");")
-    src = tmp_path / "det_abi_probe.cpp"
-    src.write_text("\n".join(tu) + "\n")
-    cxx = shutil.which("c++") or shutil.which("clang++") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    r = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.dirname(hip.DET_HEADER), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    defined = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ptd_")}
-    assert defined == ENTRIES, defined ^ ENTRIES
-    # ctypes: the gemm entries take the main header's struct; sizes come back as 64-bit integers; status returns raise in checked()
-    assert hip.DET_SIGNATURES["ptd_gemm_f16"][1][0] == ctypes.POINTER(hip.GemmParams) and hip.DET_SIGNATURES["ptd_gemm_ws_floats"][0] is ctypes.c_int64
-    L, C = hip.lib(), hip.checked()
-    assert L.ptd_abi_version() == C.ptd_abi_version() == 1
-    assert C.ptd_colsum_f16.errcheck is hip._raise_on_status and not C.ptd_abi_version.errcheck and not C.ptd_colsum_ws_floats.errcheck and not L.ptd_colsum_f16.errcheck
-    # the header and the fold's source feed the rebuild check and the build's digest
-    assert "pt_fold.h" in hip.HEADERS and "DET_HEADER" in inspect.getsource(hip.build) and "DET_HEADER" in inspect.getsource(hip.source_digest)
+def test_bindings_of_the_gemm_entries(hip):
+    """ctypes: the gemm entries take the main header's struct; sizes come back as 64-bit integers.  (The header's contract with the
+    library: tests/test_abi_cpu.py.)  The fold's source feeds the rebuild check and the build's digest."""
+    sigs = hip.ABIS["det"].signatures
+    assert sigs["ptd_gemm_f16"][1][0] == ctypes.POINTER(hip.GemmParams) and sigs["ptd_gemm_ws_floats"][0] is ctypes.c_int64
+    assert "pt_fold.h" in hip.HEADERS
 
 
 def test_size_queries(hip):
@@ -116,15 +85,17 @@ def test_product_call_sites_pass_as_many_arguments_as_declared(hip):
     """Every ``ptd_`` call in the package: positional arguments only, none starred, as many as the header declares - and every status-
     returning entry point has a call site (autodiff.py: the five reductions of the reverse pass; training.py: the gradient norm)."""
     pkg = os.path.dirname(hip.__file__)
+    sigs = hip.ABIS["det"].signatures
+    called = set(sigs) - {"ptd_abi_version"}
     sites = {}
     for f in sorted(os.listdir(pkg)):
         if f.endswith(".py"):
             for node in ast.walk(ast.parse(open(os.path.join(pkg, f)).read())):
-                if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ENTRIES - {"ptd_abi_version"}:
+                if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in called:
                     assert not node.keywords and not any(isinstance(a, ast.Starred) for a in node.args), (f, node.lineno)
-                    assert len(node.args) == len(hip.DET_SIGNATURES[node.func.attr][1]), (f, node.lineno, node.func.attr)
+                    assert len(node.args) == len(sigs[node.func.attr][1]), (f, node.lineno, node.func.attr)
                     sites.setdefault(node.func.attr, []).append(f)
-    assert set(sites) == ENTRIES - {"ptd_abi_version"}, ENTRIES - set(sites)
+    assert set(sites) == called and len(called) == 13, called - set(sites)
     assert all(len(v) == 1 for v in sites.values()), sites
     assert sites["ptd_sumsq_f32"] == ["training.py"] and all(v == ["autodiff.py"] for k, v in sites.items() if "sumsq" not in k)
 

@@ -1,5 +1,5 @@
-"""The sampler extension (include/posetraj_sampler.h, ``pts_*``) and ``DPMPP2MDiscreteScheduler`` without a GPU: the header and the
-library agree, the host-side refusals, the identities of ``coefficients``, and the solver's order on a Gaussian toy problem in fp64.
+"""The sampler extension (include/posetraj_sampler.h, ``pts_*``) and ``DPMPP2MDiscreteScheduler`` without a GPU: the two
+prototypes, the host-side refusals, the identities of ``coefficients``, and the solver's order on a Gaussian toy problem in fp64.
 
 The toy: data ``N(0, s^2)`` has the exact denoiser ``D(x, sigma) = x s^2 / (s^2 + sigma^2)`` and the probability-flow solution
 ``x(0) = x(sigma_0) s / sqrt(s^2 + sigma_0^2)``.  The recurrence ``x <- a x + b D_i + c D_{i-1}`` over the scheduler's own N-step sigma
@@ -9,42 +9,23 @@ conditions on the formulas, not measurements of this code: second order beats fi
 """
 import inspect
 import math
-import re
-import subprocess
 
 import pytest
 import torch
 
 from posetraj_amd import DPMPP2MDiscreteScheduler, EulerDiscreteScheduler, SVD_SCHEDULER_CONFIG, hip
 
-ENTRIES = {"pts_abi_version", "pts_cfg_multistep_step", "pts_multistep_step"}
 STEP_COUNTS = (1, 2, 4, 25)
 
 
 # ------------------------------------------------------------------------------------------------------- header and library
-def test_sampler_header_and_library_agree():
-    """The header is read like the other extensions, declares its version macro, the library defines every declared ``pts_`` symbol and
-    no other, the versions agree and only the two step entry points carry ``errcheck``."""
-    text = open(hip.SAMPLER_HEADER).read()
-    assert re.search(r"^#define\s+PT_SAMPLER_ABI_VERSION\s+1\s*$", text, flags=re.M)
-    version, structs, protos = hip._parse_header(text, {}, "PT_SAMPLER_ABI_VERSION", hip._STRUCTS)
-    assert version == hip.SAMPLER_ABI_VERSION == 1 and not structs and set(protos) == set(hip.SAMPLER_SIGNATURES) == ENTRIES
+def test_sampler_entry_point_prototypes():
+    """The two exact prototypes ``hip`` read from the header.  (The header's contract with the library: tests/test_abi_cpu.py.)"""
+    protos = hip.ABIS["sampler"].prototypes
     assert protos["pts_cfg_multistep_step"] == ("int", ["const void*", "int32_t", "int32_t", "const float*"] + ["float"] * 5 + ["int32_t"] * 4 +
                                                 ["float*", "float*", "void*"])
     assert protos["pts_multistep_step"] == ("int", ["const void*", "int32_t", "const float*"] + ["float"] * 5 + ["float*", "float*", "int64_t", "void*"])
-    assert not set(hip.SAMPLER_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.OPTIM_SIGNATURES) | set(hip.DET_SIGNATURES) |
-                                              set(hip.TEMPORAL_SIGNATURES) | set(hip.BATCH_SIGNATURES) | set(hip.CONTROL_SIGNATURES))
-    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    assert set(re.findall(r"\b(pts_[a-z0-9_]+)\s*\(", hdr)) == ENTRIES
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("pts_")} == ENTRIES
-    assert "sampler.hip" in hip.SOURCES and "SAMPLER_HEADER" in inspect.getsource(hip.build) and "SAMPLER_HEADER" in inspect.getsource(hip.source_digest)
-    assert hip.ABI_VERSION == 10                                                   # posetraj_hip.h did not move
-    L, C = hip.lib(), hip.checked()
-    assert L.pts_abi_version() == C.pts_abi_version() == 1
-    for name in ("pts_cfg_multistep_step", "pts_multistep_step"):
-        assert getattr(C, name).errcheck is hip._raise_on_status and not getattr(L, name).errcheck
-    assert not C.pts_abi_version.errcheck
+    assert "sampler.hip" in hip.SOURCES
 
 
 def test_sampler_entry_points_refuse_bad_arguments_on_the_host():

@@ -4,14 +4,9 @@ oracle's own temporal transformer performs, what the reference's spatial-loss ex
 B x B cross product over clip 0's residuals, which the product does NOT reproduce), and the shape checks of ``_step_inputs``."""
 import contextlib
 import io
-import re
-import subprocess
 
 import pytest
 import torch
-
-ENTRIES = {"ptb_abi_version", "ptb_add_rowvec_interleaved_f16", "ptb_colsum_interleaved_f16", "ptb_colsum_interleaved_ws_floats",
-           "ptb_colsum_interleaved_det_f16"}
 
 
 def ctx_index(B, F, S):
@@ -20,21 +15,12 @@ def ctx_index(B, F, S):
     return ((r // (F * S)) * S + r % S) % B
 
 
-def test_batch_extension_header_bindings_and_exports():
-    """The header is read like the other extensions, the library defines every declared ``ptb_`` symbol and no other, the build and
-    the source digest know the header and the source, and the host refuses what the kernels do not cover before any launch."""
-    import inspect
+def test_batch_entry_points_refuse_on_the_host_and_size_their_workspace():
+    """The host refuses what the kernels do not cover before any launch, and the workspace query follows its formula.  (The header's
+    contract with the library: tests/test_abi_cpu.py.)"""
     from posetraj_amd import hip
-    assert hip.BATCH_ABI_VERSION == 1 and set(hip.BATCH_SIGNATURES) == ENTRIES
-    assert not set(hip.BATCH_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.OPTIM_SIGNATURES) | set(hip.DET_SIGNATURES) | set(hip.TEMPORAL_SIGNATURES))
-    hdr = re.sub(r"/\*.*?\*/", " ", open(hip.BATCH_HEADER).read(), flags=re.S)
-    assert set(re.findall(r"\b(ptb_[a-z0-9_]+)\s*\(", hdr)) == ENTRIES
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ptb_")} == ENTRIES
-    assert "batch.hip" in hip.SOURCES and "BATCH_HEADER" in inspect.getsource(hip.build) and "BATCH_HEADER" in inspect.getsource(hip.source_digest)
+    assert "batch.hip" in hip.SOURCES
     L, C = hip.lib(), hip.checked()
-    assert L.ptb_abi_version() == C.ptb_abi_version() == 1
-    assert C.ptb_add_rowvec_interleaved_f16.errcheck is hip._raise_on_status and not C.ptb_abi_version.errcheck and not C.ptb_colsum_interleaved_ws_floats.errcheck
     assert L.ptb_add_rowvec_interleaved_f16(None, None, 3, 4, 64, 320, None, None) != 0 and b"null pointer" in L.pt_last_error()
     assert L.ptb_colsum_interleaved_f16(None, 3, 4, 64, 320, None, None) != 0 and b"ptb_colsum_interleaved_f16" in L.pt_last_error()
     # 2 strips x 3 classes -> 682 slabs wanted, 64 rows per slab at least: 4 slabs over the 256 rows of a class
