@@ -27,6 +27,7 @@ from .control_schedule import check_control_weight, control_plan, is_scale_seque
 from .controlnet_sdv import ControlNetSDVModel
 from .modeling import BaseOutput
 from .scheduling_euler_discrete_karras_fix import PREDICTION_TYPES, EulerDiscreteScheduler
+from .step_graphs import GraphKey, StepGraphs, StepState
 from .unet_spatio_temporal_condition_controlnet import UNetSpatioTemporalConditionControlNetModel
 
 
@@ -126,8 +127,7 @@ class StableVideoDiffusionPipelineControlNet:
         self.image_processor = _ImageProcessor(self.vae_scale_factor)
         self._guidance_scale = None
         self._num_timesteps = 0
-        self._graph_state = None                    # captured hipGraph of the per-iteration networks (denoise(use_graph=True))
-        self._control_graphs = {}                   # ... and of the other step kinds ("weighted" / "off") of the same geometry, by key
+        self._step_graphs = StepGraphs()            # captured hipGraphs of the per-iteration networks (denoise(use_graph=True)), one per kind of step
         self._side_stream = None                    # second HIP stream of denoise(overlap_streams=True)
 
     @classmethod
@@ -295,6 +295,31 @@ class StableVideoDiffusionPipelineControlNet:
         return video.float()
 
     # ------------------------------------------------------------------------------------------ the hot loop
+    def _networks_step(self, kind, sample, t, emb, cond, cam, ids, scale, level_w, overlap, _networks):
+        """ControlNet + U-Net of one iteration -> fp32 channels-last prediction [2Bc, F, h, w, 4].  The zero-convs' epilogues add the
+        ControlNet residuals straight into the U-Net's skips (no residual tensors, no add passes); with ``overlap`` the U-Net's encoder
+        half runs beside the ControlNet on a second HIP stream.  ``kind`` "plain": ``scale`` is a scalar of those epilogues; "weighted":
+        the factors in ``level_w`` with the step's scale folded in, the scalar stays 1; "off": no ControlNet, nothing to fork or join."""
+        if _networks is not None:            # tools/variants/split_cfg.py: another schedule of the same two networks (A/B only)
+            return _networks(self, sample, t, emb, cond, cam, ids, scale)
+        unet, cn = self.unet, self.controlnet
+        if kind == "off":
+            enc = unet._encode(sample, t, emb, ids)
+        else:
+            if overlap and (self._side_stream is None or self._side_stream.device != sample.device):
+                self._side_stream = torch.cuda.Stream(device=sample.device)
+            enc = unet._encode_on(self._side_stream, sample, t, emb, ids) if overlap else unet._encode(sample, t, emb, ids)
+            taps, xm = cn._features(sample, t, emb, ids, cond, cam if cn.config.camera else None)
+            if overlap:
+                unet._join_encoded(enc, self._side_stream)
+            mult = unet._multiplicity(enc, len(taps))
+            if kind == "weighted":
+                cn._accumulate_into_weighted(taps, xm, 1.0, level_w, enc["skips"], mult, enc["x"])
+            else:
+                cn._accumulate_into(taps, xm, scale, enc["skips"], mult, enc["x"])
+        pred_cl = unet._decode(enc, None, None, return_dict=False, residuals_added=True, out_f32=True)[0].permute(0, 1, 3, 4, 2)
+        return pred_cl if pred_cl.is_contiguous() else pred_cl.contiguous()
+
     @torch.no_grad()
     def denoise(self, latents: torch.Tensor, image_latents: torch.Tensor, image_embeddings: torch.Tensor,
                 controlnet_condition: torch.Tensor, num_inference_steps: int = 25, min_guidance_scale: float = 1.0,
@@ -322,8 +347,8 @@ class StableVideoDiffusionPipelineControlNet:
         A ``control_weight`` or a per-step scale sends the ControlNet steps through ``ControlNetSDVModel._accumulate_into_weighted``,
         whose factors live in device buffers: one captured graph serves every scale and every weight map."""
         plan = control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
-        Bc_, F_, h_, w_ = latents.shape[0], latents.shape[1], latents.shape[3], latents.shape[4]
-        control_weight = check_control_weight(control_weight, Bc_, F_, h_, w_)
+        (Bc, F, _, h, w), dev, out_dtype = latents.shape, latents.device, latents.dtype
+        control_weight = check_control_weight(control_weight, Bc, F, h, w)
         weighted = control_weight is not None or is_scale_sequence(controlnet_cond_scale)
         scheduled = weighted or (float(control_guidance_start), float(control_guidance_end)) != (0.0, 1.0)
         if scheduled and _networks is not None:
@@ -334,29 +359,22 @@ class StableVideoDiffusionPipelineControlNet:
             # the time ids to [Bc, 2 * 3 * D] and add_embedding's Linear raises (reference run: tests/golden/loop.npz,
             # `base_noncfg_error`).  Same exception type and message here.
             c = self.unet.config
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({latents.shape[0]}x{2 * 3 * c.addition_time_embed_dim} and "
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({Bc}x{2 * 3 * c.addition_time_embed_dim} and "
                                f"{c.projection_class_embeddings_input_dim}x{c.block_out_channels[0] * 4})")
-        dev = latents.device
-        out_dtype = latents.dtype
-        Bc, F = latents.shape[:2]
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        timesteps = self.scheduler.timesteps
+        self._num_timesteps, self.scheduler._step_index = len(self.scheduler.timesteps), None
         # per-frame guidance ramp (:506-511)
         g = torch.linspace(min_guidance_scale, max_guidance_scale, F).unsqueeze(0).to(dev, out_dtype).repeat(Bc, 1)
         self._guidance_scale = _append_dims(g, latents.ndim)
         guidance = g.to(torch.float32).contiguous()
         # micro-conditioning is hard-coded to fps 6 / bucket 128 / aug 0.02 whatever the caller asked (:513-523, Q4)
-        ids = _get_add_time_ids(0.02, torch.float32, Bc, 6, 128, unet=self.unet)
-        added_time_ids = ids.repeat(2 * Bc, 1).to(dev)                                     # torch.cat([ids] * 2)
+        added_time_ids = _get_add_time_ids(0.02, torch.float32, Bc, 6, 128, unet=self.unet).repeat(2 * Bc, 1).to(dev)   # torch.cat([ids] * 2)
         x = latents.to(torch.float32).contiguous().clone()
         il = image_latents.to(dev, torch.float16).contiguous()
         emb = image_embeddings.to(dev, torch.float16).contiguous()
         cond = controlnet_condition.to(dev, torch.float16)
         cam = None if camera_cond is None else camera_cond.to(dev, torch.float16)
-        ptype = PREDICTION_TYPES[self.scheduler.config.prediction_type]
-        sig = self.scheduler._sigmas_host
-        self._num_timesteps = len(timesteps)
-        self.scheduler._step_index = None
+        ptype, sig = PREDICTION_TYPES[self.scheduler.config.prediction_type], self.scheduler._sigmas_host
         # The three kinds of step (control_schedule): "plain" - the loop as the reference runs it, one scalar scale in the zero-convs'
         # epilogues; "weighted" - the residuals times a per-(frame, pixel) factor read from device buffers (control_weight, per-step
         # scales); "off" - outside the control window or scale 0: the U-Net alone.  Without the new arguments every step is plain.
@@ -364,163 +382,37 @@ class StableVideoDiffusionPipelineControlNet:
         step_scales = [s for _, s in plan]
         level_base = None                    # weighted: {(hh, ww): fp32 [2 Bc F hh ww]} pooled weights, pooled once per call on the device
         if "weighted" in kinds:
-            cw = torch.ones((Bc, F) + tuple(x.shape[3:]), dtype=torch.float32, device=dev) if control_weight is None else control_weight.to(dev)
-            level_base = pool_control_weight(cw, tap_sizes(x.shape[3], x.shape[4], len(self.controlnet.config.block_out_channels)))
-
-        def networks(sample, t, emb_, cond_, cam_, ids_, kind="plain", level_w=None):
-            """ControlNet + U-Net of one iteration -> fp32 channels-last prediction [2Bc, F, h, w, 4].  The ControlNet
-            residuals are accumulated straight into the U-Net's skips by the zero-convs' epilogues (no residual tensors,
-            no separate add passes); with ``overlap_streams`` the two encoders run concurrently.  ``kind`` "weighted": through
-            ``_accumulate_into_weighted`` with the factors in ``level_w``; "off": no ControlNet, nothing to overlap or join."""
-            if _networks is not None:        # tools/variants/split_cfg.py: another schedule of the same two networks (A/B only)
-                return _networks(self, sample, t, emb_, cond_, cam_, ids_, controlnet_cond_scale)
-            if kind == "off":
-                enc = self.unet._encode(sample, t, emb_, ids_)
-                pred = self.unet._decode(enc, None, None, return_dict=False, residuals_added=True, out_f32=True)[0]
-                pred_cl = pred.permute(0, 1, 3, 4, 2)
-                return pred_cl if pred_cl.is_contiguous() else pred_cl.contiguous()
-            main = torch.cuda.current_stream(dev)
-            if overlap_streams:
-                # The U-Net's encoder half does not depend on the ControlNet (its outputs are added to the skips and to
-                # the mid block's output afterwards): run it on a second HIP stream while the ControlNet runs on this
-                # one.  Same kernels, same results; the two streams' workgroups fill each other's tail rounds and
-                # memory-bound phases.  (Inside a hipGraph capture this becomes two branches of the graph.)
-                if self._side_stream is None or self._side_stream.device != dev:
-                    self._side_stream = torch.cuda.Stream(device=dev)
-                side = self._side_stream
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    enc = self.unet._encode(sample, t, emb_, ids_)
-            else:
-                enc = self.unet._encode(sample, t, emb_, ids_)
-            taps, xm = self.controlnet._features(sample, t, emb_, ids_, cond_,
-                                                 cam_ if self.controlnet.config.camera else None)
-            if overlap_streams:
-                main.wait_stream(side)
-                for tns in [enc["x"], enc["ctx"].temb, enc["ctx"].xattn] + list(enc["skips"]):
-                    if tns is not None:
-                        tns.record_stream(main)               # allocated on the side stream, consumed on this one
-                        if getattr(tns, "lo", None) is not None:
-                            tns.lo.record_stream(main)        # ... and so is the low half of a wide-stream tensor
-            if kind == "weighted":           # the step's scale is folded into level_w before the launch (below): the scalar stays 1
-                self.controlnet._accumulate_into_weighted(taps, xm, 1.0, level_w, enc["skips"],
-                                                          self.unet._multiplicity(enc, len(taps)), enc["x"])
-            else:
-                self.controlnet._accumulate_into(taps, xm, controlnet_cond_scale, enc["skips"],
-                                                 self.unet._multiplicity(enc, len(taps)), enc["x"])
-            pred = self.unet._decode(enc, None, None, return_dict=False, residuals_added=True, out_f32=True)[0]
-            pred_cl = pred.permute(0, 1, 3, 4, 2)                                          # [2Bc, F, h, w, 4] contiguous
-            return pred_cl if pred_cl.is_contiguous() else pred_cl.contiguous()
-
-        # The ~2 500 launches of ControlNet + U-Net are captured ONCE into a hipGraph over static input buffers and
-        # replayed per iteration (and for later clips of the same geometry); the two fused loop kernels around them
-        # carry the per-step scalars and stay eager.  The condition encoder is not in the graph: it runs once per clip
-        # and refreshes its cached output in place.
-        # One state per KIND of step: the plain one is ``self._graph_state`` under the key it always had (the scale is baked into its
-        # epilogues); "weighted" and "off" live in ``self._control_graphs`` under the same key with the kind in the scale's place -
-        # their launches do not depend on the scale: 25 distinct scales, or another weight map, replay one graph.  A state is found
-        # or captured at the first step of its kind in this call; later captures of a geometry share the first one's memory pool
-        # (the kinds replay one after the other on one stream and each prediction is consumed before the next replay), so the
-        # U-Net's activations are not held twice.
-        def graph_key(kind):
-            return (Bc, F, tuple(x.shape[3:]), tuple(cond.shape), None if cam is None else tuple(cam.shape),
-                    float(controlnet_cond_scale) if kind == "plain" else kind, id(self.unet), id(self.controlnet), self.unet._generation,
-                    self.controlnet._generation, bool(overlap_streams), getattr(_networks, '__name__', None), ops.dispatch_key())
-
-        same_geometry = lambda k1, k2: k1[:5] + k1[6:] == k2[:5] + k2[6:]
-        live = {}                            # kind -> the state this call uses: graph state (use_graph) or the eager step's buffers
-
-        def refresh_weights(st):
-            """This call's pooled weights into the buffers the state owns, in place (a captured graph reads those addresses)."""
-            if "wbase" not in st:
-                st["wbase"] = {sz: b.clone() for sz, b in level_base.items()}
-                st["wbuf"] = {sz: torch.empty_like(b) for sz, b in level_base.items()}
-            else:
-                for sz, b in level_base.items():
-                    st["wbase"][sz].copy_(b)
-            st["folded"] = None
-
-        def graph_state(kind, k, t):
-            key = graph_key(kind)
-            if kind == "plain":
-                gs = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
-            else:
-                gs = self._control_graphs.get(key)
-            on = kind != "off"               # an off step reads neither the control maps nor the camera
-            if gs is None:
-                gs = dict(key=key, xin=torch.empty((2 * Bc, F, x.shape[3], x.shape[4], 8), dtype=torch.float16, device=dev),
-                          t=torch.zeros(1, dtype=torch.float32, device=dev), emb=emb.clone(), cond=cond.clone() if on else None,
-                          cam=None if cam is None or not on else cam.clone(), ids=added_time_ids.clone())
-            else:
-                gs["emb"].copy_(emb); gs["ids"].copy_(added_time_ids)
-                if on:
-                    gs["cond"].copy_(cond)
-                    if cam is not None:
-                        gs["cam"].copy_(cam)
-            if on:
-                # once per clip: the condition encoder, eagerly (the in-place edits above bumped the tensors' versions),
-                # into a buffer this graph state owns: the captured graph reads that address whatever the ControlNet's
-                # cache holds after other (eager) calls
-                gs["cond_embed"] = self.controlnet._cond_embedding(gs["cond"], gs["cam"] if self.controlnet.config.camera else None,
-                                                                  out=gs.get("cond_embed"))
-            if kind == "weighted":
-                refresh_weights(gs)
-                for sz, b in gs["wbase"].items():            # (the warm-up and the capture read defined values)
-                    gs["wbuf"][sz].copy_(b)
-            if "graph" not in gs:
-                ops.scale_concat_input(x, il, sig[k], out=gs["xin"])
-                gs["t"].fill_(float(t))
-                run = lambda: networks(gs["xin"].permute(0, 1, 4, 2, 3), gs["t"], gs["emb"], gs["cond"], gs["cam"], gs["ids"], kind, gs.get("wbuf"))
-                warm = torch.cuda.Stream(device=dev)
-                warm.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(warm):                # warm-up: weight-only caches, allocator sizing
-                    run()
-                torch.cuda.current_stream(dev).wait_stream(warm)
-                others = [s_ for s_ in ([] if kind == "plain" else [self._graph_state]) + list(self._control_graphs.values())
-                          if s_ is not None and "graph" in s_ and same_geometry(s_["key"], key)]
-                g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_, pool=others[0]["graph"].pool() if others else None):
-                    gs["pred"] = run()
-                gs["graph"] = g_
-                if kind == "plain":
-                    self._graph_state = gs
-                else:                                        # keep the dict small: the kinds of the current geometry only
-                    self._control_graphs = {k_: s_ for k_, s_ in self._control_graphs.items() if same_geometry(k_, key)}
-                    self._control_graphs[key] = gs
-            return gs
-
+            cw = torch.ones((Bc, F, h, w), dtype=torch.float32, device=dev) if control_weight is None else control_weight.to(dev)
+            level_base = pool_control_weight(cw, tap_sizes(h, w, len(self.controlnet.config.block_out_channels)))
+        # One StepState per kind this call uses: with ``use_graph`` found in, or captured into, ``self._step_graphs`` under its key.
+        run = lambda st, sample, t_: self._networks_step(st.kind, sample, t_, st.emb, st.cond, st.cam, st.ids, controlnet_cond_scale,
+                                                         st.wbuf, overlap_streams, _networks)
+        geometry = GraphKey(Bc=Bc, F=F, hw=(h, w), cond_shape=tuple(cond.shape), cam_shape=None if cam is None else tuple(cam.shape),
+                            kind=None, scale=None, unet=id(self.unet), controlnet=id(self.controlnet), unet_gen=self.unet._generation,
+                            controlnet_gen=self.controlnet._generation, overlap=bool(overlap_streams),
+                            networks_name=getattr(_networks, '__name__', None), dispatch=ops.dispatch_key()) if use_graph else None
+        live = {}
         # The sampler: a scheduler of order 2 (DPMPP2MDiscreteScheduler) takes the multistep kernel with its own host-computed
         # coefficients and one more latent-sized tensor, the previous denoised estimate; any other takes the Euler kernel.  Both run
         # after the networks, outside the captured graphs: one graph serves both schedulers.
         multistep = getattr(self.scheduler, "order", 1) == 2
         d_prev = torch.empty_like(x) if multistep else None
-        for i in range(len(timesteps)):
+        for i in range(self._num_timesteps):
             t = self.scheduler._timesteps_host[i]
             if self.scheduler._step_index is None:
                 self.scheduler._init_step_index(t)
             k = self.scheduler._step_index
             kind = kinds[i]
             st = live.get(kind)
-            if st is None:
-                if use_graph:
-                    st = graph_state(kind, k, t)
-                else:
-                    st = {}
-                    if kind == "weighted":
-                        refresh_weights(st)
-                live[kind] = st
-            if kind == "weighted" and st["folded"] != step_scales[i]:
-                for sz, b in st["wbase"].items():            # this step's scale, folded into the factors the kernels read
-                    torch.mul(b, step_scales[i], out=st["wbuf"][sz])
-                st["folded"] = step_scales[i]
-            if use_graph:
-                ops.scale_concat_input(x, il, sig[k], out=st["xin"])
-                st["t"].fill_(float(t))
-                st["graph"].replay()
-                pred_cl = st["pred"]
-            else:
-                xin = ops.scale_concat_input(x, il, sig[k])                                # [2Bc, F, h, w, 8]
-                pred_cl = networks(xin.permute(0, 1, 4, 2, 3), t, emb, cond, cam, added_time_ids, kind, st.get("wbuf"))   # [2Bc, F, 8, h, w] view
+            if st is None:                   # the first step of its kind in this call
+                key = geometry and geometry._replace(kind=kind, scale=float(controlnet_cond_scale) if kind == "plain" else None)
+                st = live[kind] = (key and self._step_graphs.get(key)) or StepState(kind, run, key)
+                st.load(emb, added_time_ids, cond, cam, level_base, self.controlnet)
+                if use_graph and st.graph is None:
+                    st.capture(self._step_graphs.pool_for(key), x, il, sig[k], t)
+                    self._step_graphs.insert(key, st)
+            st.fold(step_scales[i])
+            pred_cl = st.step(x, il, sig[k], t)                                            # [2Bc, F, h, w, 4] fp32
             if multistep:                    # DPM-Solver++(2M): this call's first step has no previous estimate (c = 0: d_prev is written, not read)
                 ops.cfg_multistep_step(pred_cl, guidance, self.scheduler.coefficients(k, first=i == 0), x, d_prev)
             else:

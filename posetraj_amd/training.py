@@ -509,9 +509,8 @@ class ControlNetTrainer:
         if self.encoder_stream:
             if self._enc_stream is None:
                 self._enc_stream = torch.cuda.Stream()
-            self._enc_stream.wait_stream(main)
-            with torch.cuda.stream(self._enc_stream), torch.no_grad():
-                state = unet._encode(inp, timesteps, I["ehs"], ids)
+            with torch.no_grad():
+                state = unet._encode_on(self._enc_stream, inp, timesteps, I["ehs"], ids)
         if "traj" not in I:                                   # staged here, behind the encoder's launches: the device is busy meanwhile
             I["traj"] = I.pop("traj_src").to(dev, torch.float16)
         if self._packs_pending:                               # the packs re-written behind the last optimizer step (their own stream)
@@ -561,12 +560,7 @@ class ControlNetTrainer:
             with torch.no_grad():
                 state = unet._encode(inp, timesteps, I["ehs"], ids)
         else:
-            main.wait_stream(self._enc_stream)
-            for tns in [state["x"], state["ctx"].temb, state["ctx"].xattn] + list(state["skips"]):
-                if tns is not None:
-                    tns.record_stream(main)                   # allocated on the encoder's stream, consumed on this one
-                    if getattr(tns, "lo", None) is not None:
-                        tns.lo.record_stream(main)
+            unet._join_encoded(state, self._enc_stream)
         mult = unet._multiplicity(state, len(outs))
         pred = self.decoder.run(tape, state, mult, outs, mid, emb_silu, ehs16, checkpoint=self._ckpt_dec)
         lt = loss_of(pred, noisy, lat, F, 1.0)

@@ -81,7 +81,24 @@ class UNetSpatioTemporalConditionControlNetModel(HipModel):
 
     # The encoder half (conv_in, down blocks, mid block) never sees the ControlNet outputs - the reference adds them to
     # the collected skips and to the mid block's output (:451-469) - so it is independent of the ControlNet forward:
-    # the pipeline runs the two concurrently on two HIP streams (pipeline...: networks()).
+    # the pipeline and the trainer run the two concurrently on two HIP streams (two branches of a captured hipGraph): same kernels,
+    # same results, the two streams' workgroups fill each other's tail rounds and memory-bound phases.
+    def _encode_on(self, side, *args):
+        """Fork: ``_encode(*args)`` on the stream ``side``, behind what the current stream holds so far."""
+        side.wait_stream(torch.cuda.current_stream(side.device))
+        with torch.cuda.stream(side):
+            return self._encode(*args)
+
+    @staticmethod
+    def _join_encoded(state, side):
+        """Join: the current stream waits for ``side`` and takes over the tensors of ``state`` that were allocated there."""
+        main = torch.cuda.current_stream(side.device)
+        main.wait_stream(side)
+        for tns in [state["x"], state["ctx"].temb, state["ctx"].xattn] + list(state["skips"]):
+            for part in (tns, getattr(tns, "lo", None)):      # ... and the low half of a wide-stream tensor
+                if part is not None:
+                    part.record_stream(main)
+
     def _encode(self, sample, timestep, encoder_hidden_states, added_time_ids, half=None):
         ctx, x, (Bc, F, h, w) = self._prologue(sample, timestep, encoder_hidden_states, added_time_ids, half=half)
         N = Bc * F

@@ -346,14 +346,14 @@ def test_loop_weight_scales_and_window_together_reuse_their_graphs_for_another_w
     into a graph would reproduce the first run."""
     pipe = bench.new_pipe()
     first = {False: bench.run("D", False, pipe), True: bench.run("D", True, pipe)}
-    states = dict(pipe._control_graphs)
-    graphs = {k: s["graph"] for k, s in states.items()}
-    assert sorted(k[5] for k in states) == ["off", "weighted"] and pipe._graph_state is None
-    assert states[[k for k in states if k[5] == "off"][0]]["graph"].pool() == states[[k for k in states if k[5] == "weighted"][0]]["graph"].pool()
+    states = {k: pipe._step_graphs.get(k) for k in pipe._step_graphs}
+    graphs = {k: s.graph for k, s in states.items()}
+    assert sorted(k.kind for k in states) == ["off", "weighted"] and pipe._step_graphs.of_kind("plain") is None
+    assert pipe._step_graphs.of_kind("off").graph.pool() == pipe._step_graphs.of_kind("weighted").graph.pool()
     _check_scenario(bench, "D", capsys, first)
     second = {False: bench.run("D2", False, pipe), True: bench.run("D2", True, pipe)}
-    assert set(pipe._control_graphs) == set(states)
-    assert all(pipe._control_graphs[k] is states[k] and pipe._control_graphs[k]["graph"] is graphs[k] for k in states)
+    assert set(pipe._step_graphs) == set(states)
+    assert all(pipe._step_graphs.get(k) is states[k] and states[k].graph is graphs[k] for k in states)
     _check_scenario(bench, "D2", capsys, second)
     assert P.rel_l2(bench.oracle("D2")[-1], bench.oracle("D")[-1]) >= 4 * max(bench.bound()[1])       # the two maps are told apart
 
@@ -402,7 +402,7 @@ def test_steps_outside_the_window_do_not_launch_the_controlnet(bench):
     finally:
         for k in ("_features", "_accumulate_into", "_accumulate_into_weighted"):
             del cn.__dict__[k]
-    assert pipe._graph_state is None and not pipe._control_graphs
+    assert len(pipe._step_graphs) == 0
 
 
 def test_new_arguments_reach_call_and_the_camera_pipeline(bench_cam):

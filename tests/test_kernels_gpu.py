@@ -705,7 +705,7 @@ def test_wide_stream_pair_output_and_pair_residual(ops, dev, cfg):
     x, w, b = h16(M, K, g=g, dev=dev), h16(N, K, g=g, scale=K ** -0.5, dev=dev), h16(N, g=g, dev=dev)
     r_hi = h16(M, N, g=g, dev=dev)
     r_lo = (h16(M, N, g=g, dev=dev) * 2.0 ** -12).half()
-    res = r_hi.clone(); res.lo = r_lo
+    res = r_hi.clone(); ops._attach_lo(res, r_lo)             # (records the buffer's write count, like a pair the library makes)
     hip.check(hip.lib().pt_igemm_force_config(cfg))
     try:
         pw = pack_linear(w, b, dev)
@@ -724,7 +724,7 @@ def test_wide_stream_pair_output_and_pair_residual(ops, dev, cfg):
     if cfg == -1:                                                                       # split-K reducer (level-3 conv)
         xc = h16(28, 9, 16, 1280, g=g, dev=dev)
         wc, bc = h16(1280, 1280, 3, 3, g=g, scale=(9 * 1280) ** -0.5, dev=dev), h16(1280, g=g, dev=dev)
-        rc = h16(28 * 9 * 16, 1280, g=g, dev=dev); rc.lo = (h16(28 * 9 * 16, 1280, g=g, dev=dev) * 2.0 ** -12).half()
+        rc = h16(28 * 9 * 16, 1280, g=g, dev=dev); ops._attach_lo(rc, (h16(28 * 9 * 16, 1280, g=g, dev=dev) * 2.0 ** -12).half())
         yc = ops.igemm(xc, pack_conv2d(wc, bc, dev), geom=(28, 9, 16), res=rc, wide=True)
         refc = F.conv2d(xc.double().permute(0, 3, 1, 2), wc.double(), bc.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, 1280)
         refc = refc + rc.double() + rc.lo.double()

@@ -239,7 +239,7 @@ def test_hipgraph_replay_equals_eager_and_is_reused_across_clips(dev):
         # ControlNet and the U-Net's encoder half on two HIP streams: same kernels, bit-identical results
         assert torch.equal(outs[(clip, "eager")], outs[(clip, "eager2")])
         assert torch.equal(outs[(clip, "eager")], outs[(clip, "graph2")])
-    assert pipe._graph_state is not None and "graph" in pipe._graph_state
+    assert pipe._step_graphs.of_kind("plain") is not None and pipe._step_graphs.of_kind("plain").graph is not None
     assert not torch.equal(outs[(0, "graph")], outs[(1, "graph")])
 
 
@@ -315,7 +315,7 @@ def test_hipgraph_is_reused_for_a_second_clip(dev):
         c1 = (torch.rand(1, 14, 3, 64, 64, generator=g) * 2 - 1).half()
         cond = torch.cat([c1, c1]).to(dev)
         out_g = pipe.denoise(lat, il, emb, cond, num_inference_steps=2, use_graph=True, overlap_streams=True)
-        graphs.append(pipe._graph_state["graph"])
+        graphs.append(pipe._step_graphs.of_kind("plain").graph)
         if clip == 1:
             # an eager ControlNet call with ANOTHER condition geometry between replays replaces the ControlNet's cached
             # condition embedding; the graph owns its own embedding buffer, so the next replay must still be right
@@ -352,7 +352,7 @@ def test_hipgraph_is_recaptured_when_a_dispatch_switch_flips(dev):
         for on in (True, False):
             ops.FUSED_PRE = on
             outs[on] = pipe.denoise(lat, il, emb, cond, num_inference_steps=2, use_graph=True, overlap_streams=True)
-            keys[on] = pipe._graph_state["key"]
+            keys[on] = pipe._step_graphs.of_kind("plain").key
             assert torch.equal(outs[on], pipe.denoise(lat, il, emb, cond, num_inference_steps=2, use_graph=False, overlap_streams=False)), on
     finally:
         ops.FUSED_PRE = keep

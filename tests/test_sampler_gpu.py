@@ -398,7 +398,7 @@ def test_the_scheduler_picks_the_step_kernel_and_both_share_one_graph(rig, monke
         calls.update(euler=0, multistep=0)
         e = rig.denoise(pipe, STEPS, graph)
         assert (calls["euler"], calls["multistep"]) == (STEPS, 0)
-    state, graph_obj = pipe._graph_state, pipe._graph_state["graph"]
+    state, graph_obj = pipe._step_graphs.of_kind("plain"), pipe._step_graphs.of_kind("plain").graph
     euler_config = pipe.scheduler.config
     pipe.scheduler = DPMPP2MDiscreteScheduler.from_config(pipe.scheduler.config)
     assert pipe.scheduler.config == euler_config
@@ -410,7 +410,7 @@ def test_the_scheduler_picks_the_step_kernel_and_both_share_one_graph(rig, monke
         assert cs[0] == 0.0 and all(c < 0.0 for c in cs[1:-1]) and cs[-1] == 0.0 and calls["args"][-1][0][2:] == (0.0, 1.0, 0.0)
         assert all(a[2] is calls["args"][0][2] for a in calls["args"]) and calls["args"][0][2].shape == calls["args"][0][1].shape
         assert torch.equal(m.cpu(), rig.hip("dpmpp2m", graph)[-1])
-    assert pipe._graph_state is state and pipe._graph_state["graph"] is graph_obj and not pipe._control_graphs
+    assert pipe._step_graphs.of_kind("plain") is state and state.graph is graph_obj and len(pipe._step_graphs) == 1
     assert torch.equal(e.cpu(), rig.hip("euler", True)[-1]) and not torch.equal(e, m)
 
 

@@ -56,4 +56,4 @@ print(json.dumps({"workload": a.workload, "geometry": f"{a.frames}x{height}x{wid
                                        "off": round((res["window_end_0.5"] - n_on * plain_it) / n_off, 2),
                                        "off_from_weighted_runs": round((res["weighted_window_end_0.5"] - n_on * weighted_it) / n_off, 2)},
                   "weighted_over_plain": round(weighted_it / plain_it, 4), "off_over_plain": round((res["window_end_0.5"] - n_on * plain_it) / n_off / plain_it, 4),
-                  "graph_states": 1 + len(pipe._control_graphs), "max_memory_allocated_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
+                  "graph_states": len(pipe._step_graphs), "max_memory_allocated_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))

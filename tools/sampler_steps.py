@@ -84,12 +84,12 @@ if "b" in a.part:
     for name, sched, n in configs:                                  # warm-up: the first one captures the graph all three replay
         _, out = clip(sched, n)
         assert bool(torch.isfinite(out).all()), name
-    graph = pipe._graph_state["graph"]
+    graph = pipe._step_graphs.of_kind("plain").graph
     times = {name: [] for name, _, _ in configs}
     for _ in range(a.clips):
         for name, sched, n in configs:
             times[name].append(clip(sched, n)[0])
-    assert pipe._graph_state["graph"] is graph                       # one captured graph served every clip
+    assert pipe._step_graphs.of_kind("plain").graph is graph     # one captured graph served every clip
     say()
     say(f"(b) full width, {a.frames} x {height} x {width}, random-init SVD U-Net + ControlNet, hipGraph + two streams: ms per clip of `denoise`,")
     say(f"    {a.clips} clips each, alternated in one process after one warm-up clip each, synchronised around every clip")
