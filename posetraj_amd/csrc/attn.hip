@@ -201,7 +201,9 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
                     for (int j = 0; j < 4; ++j) mx = fmaxf(mx, st[kb][qb][j]);
                 mx = query_max(mx);
                 const float delta = kt == 0 ? mx : fmaxf(mx, 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(PRE ? -delta : -delta * cexp);
+                // tile 0 scales accumulators that are still zero: by 1, not by 2^-mx, which is +inf (0 x inf = NaN) for a first tile
+                // whose scores all lie below -128 log2 units
+                const float alpha = kt == 0 ? 1.f : __builtin_amdgcn_exp2f(PRE ? -delta : -delta * cexp);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     lacc[qb][j] *= alpha; negm[qb][j] -= delta;
