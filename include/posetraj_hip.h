@@ -64,7 +64,16 @@ int pt_set_zero_page(const void* dev_zeros_256B);
  *   res_lo, vec, blend, out_lo, out_f32, act != 0, cs_cols, C0 % 64 != 0 or a padded K; it never runs split-K.  Results
  *   differ from mode 1 by the rounding of the folded weights (summed in fp32, rounded to fp16 once).
  * vec_mode: 0 none; 1 vidx = m / vG (per frame / per clip row vectors); 2 the batch-interleaved index of the
- *   temporal cross-attention context (models/modified_svd.py:152-159): vidx = ((m / vFS) * vS + m % vS) % vB.
+ *   temporal cross-attention context (models/modified_svd.py:152-159): vidx = ((m / vFS) * vS + m % vS) % vB;
+ *   3 "clip-local interleave" - the same context for a batch of vG INDEPENDENT clips, a departure from the reference made on
+ *   purpose (opt-in: independent_clips=True).  `vec` holds vB rows, halves-major: row half * vG + clip (vB = 2 vG under
+ *   classifier-free guidance, vB = vG for a batch without halves); with b = m / vFS the batch element of row m,
+ *       vidx = (((b / vG) * vS + m % vS) % (vB / vG)) * vG + b % vG
+ *   - clip c reads exactly the rows, in the same interleave, that it reads in a call of its own, never another clip's.
+ *   vG = 1 is mode 2 (by algebra), so one clip computes what it always did.  Needs vG >= 1, vB % vG == 0 and vFS, vS, vB > 0
+ *   (an error naming the entry point otherwise); vG is unused in mode 2.  Mode 3 runs in the plain-loop kernels (instances of
+ *   their own) and in the split-K reducer; the pipelined kernels are compiled without it.  No change of PT_ABI_VERSION: a new value of an
+ *   existing field, like the temporal attention's frame range.
  * Replaces: nn.Conv2d / nn.Conv3d((3,1,1)) / nn.Linear dispatches of diffusers' ResnetBlock2D,
  *   TemporalResnetBlock, Downsample2D, Upsample2D, Attention.to_{q,k,v,out}, FeedForward/GEGLU, proj_in/out
  *   (constructed at models/controlnet_sdv.py:352-391, models/unet_spatio_temporal_condition_controlnet.py:169-245),
@@ -146,7 +155,9 @@ typedef struct pt_ffn_params {
     const void* blend; int32_t ldb; float alpha;
     /* optional (pre_w != NULL): start one step earlier in the transformer block.  `x` then holds the ATTENTION OUTPUT rows and the
      * kernel's prologue computes  h = x . pre_w^T + pre_b + pre_res + pre_vec[idx(m)]  (the attention's output projection with its
-     * residual and the collapsed cross-attention row vector, indexed like pt_igemm_params.vec),  LayerNorm(h; ln_gamma, ln_beta,
+     * residual and the collapsed cross-attention row vector, indexed like pt_igemm_params.vec: pre_vec_mode 1, 2 or 3 with the
+     * same meaning and the same argument rules for pre_vG / pre_vFS / pre_vS / pre_vB; the tail's own `vec` above takes modes 1
+     * and 2, mode 3 there is refused),  LayerNorm(h; ln_gamma, ln_beta,
      * ln_eps)  as the feed-forward's input, and uses h itself as the feed-forward's residual (`res` must be NULL):
      *     out = tail( W2 . geglu(W1 . LN(h) + b1) + b2 + h )          - attn1.to_out + residual, norm3, ff + residual of
      * BasicTransformerBlock / TemporalBasicTransformerBlock (modified_svd.py:79-82,97-104) in one launch.  h is kept in fp32. */

@@ -68,6 +68,17 @@ class Ctx:
     half: Optional[int] = None                 # which slice of the full batch this forward covers (None: the whole batch)
     xattn_full: Optional[torch.Tensor] = None  # [B_total, sum C]
     xattn_full_swapped: Optional[torch.Tensor] = None   # rows rolled by one: the table a half with an odd row offset sees
+    # ``independent_clips=True`` (pipeline / trainer; NOT the reference's behaviour): the batch holds ``clips`` clips, halves-major
+    # (row ``half * clips + clip``: ``B = 2 clips`` under CFG, ``B = clips`` in the trainer's frozen encoder), and the temporal
+    # cross-attention hands each clip its own context rows (``vec_mode=3``) instead of the batch-wide interleave.  One clip: mode 2.
+    clips: int = 1
+    independent: bool = False
+
+    def __post_init__(self):
+        if self.independent and self.half is not None:
+            raise ValueError("independent_clips does not go with a split-CFG forward (`half`): that schedule takes one clip")
+        if self.independent and (self.clips < 1 or self.B % self.clips):
+            raise ValueError(f"independent_clips: a batch of {self.B} rows does not divide into {self.clips} clips")
 
 
 class SpatioTemporalResBlock:
@@ -249,12 +260,17 @@ class TransformerSpatioTemporalModel:
                 tbl = ldx
             else:                                            # global index ((b + half * B) * S + s) mod B_total with B_total = 2 B, B = 1
                 tbl = ctx.xattn_full if (ctx.half * B * S) % ctx.xattn_full.shape[0] == 0 else ctx.xattn_full_swapped
+            # the context row of token (b, f, s): the reference's batch-wide interleave (mode 2), or - independent clips, more than one -
+            # the same interleave inside each clip's own rows (mode 3, include/posetraj_hip.h)
+            idx = dict(vec_mode=2, vFS=F * S, vS=S, vB=tbl.shape[0])
+            if ctx.independent and ctx.clips > 1:
+                idx.update(vec_mode=3, vG=ctx.clips)
             # ff(norm3(u)) + u, then AlphaBlender(hs, .)
             if ops.FUSED_PRE and ops.ffn_fusable(L.tf1, L.tf2) and getattr(u, "lo", None) is None:
                 h = ops.ffn_geglu(a, L.tf1, L.tf2, blend=hs, alpha=self.alpha,
-                                  pre=dict(w=L.to, res=u, vec=tbl[:, L.tx_off:L.tx_off + C], vec_mode=2, vFS=F * S, vS=S, vB=tbl.shape[0], ln=L.tln3))
+                                  pre=dict(w=L.to, res=u, vec=tbl[:, L.tx_off:L.tx_off + C], ln=L.tln3, **idx))
             else:
-                u = ops.igemm(a, L.to, res=u, vec=tbl[:, L.tx_off:L.tx_off + C], vec_mode=2, vFS=F * S, vS=S, vB=tbl.shape[0])
+                u = ops.igemm(a, L.to, res=u, vec=tbl[:, L.tx_off:L.tx_off + C], **idx)
                 h = self._feed_forward(ops.layernorm(u, *L.tln3), L.tf1, L.tf2, N, S, res=u, blend=hs, alpha=self.alpha)
         # (the block's own output is a plain fp16 tensor: widening it buys 1 % of the error for a fifth of the cost)
         y = ops.igemm(h, self.proj_out, res=xt)

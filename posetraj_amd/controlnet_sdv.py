@@ -150,10 +150,11 @@ class ControlNetSDVModel(HipModel):
         return ControlNetOutput(down_block_res_samples=outs, mid_block_res_sample=mid)
 
     def _features(self, sample, timestep, encoder_hidden_states, added_time_ids, controlnet_cond=None, camera_cond=None,
-                  half=None):
+                  half=None, independent_clips: int = 0):
         """conv_in (+ condition embedding), down blocks, mid block (``:551-628``): the 12 taps and the mid feature,
         channels-last, before the zero-convs."""
-        ctx, x, (Bc, F, h, w) = self._prologue(sample, timestep, encoder_hidden_states, added_time_ids, half=half)
+        ctx, x, (Bc, F, h, w) = self._prologue(sample, timestep, encoder_hidden_states, added_time_ids, half=half,
+                                               independent_clips=independent_clips)
         N = Bc * F
         res = None
         if controlnet_cond is not None:                                           # :596-599

@@ -131,7 +131,15 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
             const int row = min(m0 + wr * 32 + r * 16 + frow, p.M - 1);
             const f16* rp = fp.pres + (size_t)row * fp.ldpr + wc * 160 + 4 * fq;
             int vi = 0;
-            if (fp.pvec) vi = fp.pvec_mode == 1 ? row / fp.pvG : ((row / fp.pvFS) * fp.pvS + row % fp.pvS) % fp.pvB;
+            // igemm_tail.h: vec_index.  Modes 2 and 3 share one expression here (twice per lane and launch): the host hands mode 2 over as
+            // pvG = 1 and mode 3 with the table rows per clip in pvB
+            if (fp.pvec) {
+                if (fp.pvec_mode == 1) vi = row / fp.pvG;
+                else {                                       // b = h pvG + clip
+                    const int b = row / fp.pvFS, h = b / fp.pvG;
+                    vi = ((h * fp.pvS + row % fp.pvS) % fp.pvB) * fp.pvG + (b - h * fp.pvG);
+                }
+            }
             const f16* vp = fp.pvec ? fp.pvec + (size_t)vi * fp.ldpv + wc * 160 + 4 * fq : (const f16*)kp.zeros;
             const int vstep = fp.pvec ? 16 : 0;
 #pragma unroll
@@ -436,7 +444,7 @@ __global__ __launch_bounds__(512, 2) void ffn320_kernel(const FParams fp) {
     {
         int lane_t = lane;                                   // (opaque: keeps the tail's lane-derived values below the chunk loop)
         asm volatile("" : "+v"(lane_t));
-        igemm_epilogue<CF, VAR>(kp, acc2, smem, m0, 0, wave, lane_t);
+        igemm_epilogue<CF, VAR, false, false>(kp, acc2, smem, m0, 0, wave, lane_t);   // (the tail's row vector: modes 1 and 2)
     }
 #undef FF_ST
     __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
@@ -462,6 +470,7 @@ extern "C" int pt_ffn_geglu_f16(const pt_ffn_params* pp, void* stream) {
              "pt_ffn_geglu_f16: operands must be 16-byte aligned");
     PT_CHECK((!q.res || q.ldr % 8 == 0) && (!q.vec || q.ldv % 8 == 0) && (!q.blend || q.ldb % 8 == 0), "pt_ffn_geglu_f16: side-input pitches must be multiples of 8");
     PT_CHECK(q.vec_mode == 0 || q.vec, "pt_ffn_geglu_f16: vec_mode without vec");
+    PT_CHECK(q.vec_mode != 3, "pt_ffn_geglu_f16: vec_mode 3 serves pre_vec (pre_vec_mode) only; the tail's `vec` takes modes 1 and 2");
     PT_CHECK((q.res ? 1 : 0) + (q.vec ? 1 : 0) + (q.blend ? 1 : 0) <= 2, "pt_ffn_geglu_f16: at most two side inputs");
     FParams fp;
     memset(&fp, 0, sizeof(fp));
@@ -486,12 +495,15 @@ extern "C" int pt_ffn_geglu_f16(const pt_ffn_params* pp, void* stream) {
     const bool pre = q.pre_w != nullptr;
     if (pre) {
         PT_CHECK(q.pre_res && q.ln_gamma && q.ln_beta && !q.res, "pt_ffn_geglu_f16: pre_w needs pre_res, ln_gamma, ln_beta and no `res` (the block's own h is the residual)");
-        PT_CHECK(q.pre_kpad == 320 && q.pre_ldr % 8 == 0 && (!q.pre_vec || (q.pre_ldv % 8 == 0 && (q.pre_vec_mode == 1 ? q.pre_vG > 0 : (q.pre_vec_mode == 2 && q.pre_vFS > 0 && q.pre_vS > 0 && q.pre_vB > 0)))),
-                 "pt_ffn_geglu_f16: bad pre-projection arguments");
+        PT_CHECK(q.pre_kpad == 320 && q.pre_ldr % 8 == 0 && (!q.pre_vec || (q.pre_ldv % 8 == 0 && (q.pre_vec_mode == 1 ? q.pre_vG > 0 : (q.pre_vec_mode == 2 && q.pre_vFS > 0 && q.pre_vS > 0 && q.pre_vB > 0) ||
+                                                                                                                     (q.pre_vec_mode == 3 && vec_clip_local_ok(q.pre_vG, q.pre_vFS, q.pre_vS, q.pre_vB))))),
+                 "pt_ffn_geglu_f16: bad pre-projection arguments (pre_vec_mode 3 needs pre_vG >= 1, pre_vB %% pre_vG == 0 and pre_vFS, pre_vS, pre_vB > 0)");
         PT_CHECK(al16(q.pre_w) && al16(q.pre_b) && al16(q.pre_res) && al16(q.pre_vec) && al16(q.ln_gamma) && al16(q.ln_beta), "pt_ffn_geglu_f16: pre-projection operands must be 16-byte aligned");
         fp.wo = (const f16*)q.pre_w; fp.bo = (const f16*)q.pre_b; fp.kpado = q.pre_kpad;
         fp.pres = (const f16*)q.pre_res; fp.ldpr = q.pre_ldr;
         fp.pvec = (const f16*)q.pre_vec; fp.ldpv = q.pre_ldv; fp.pvec_mode = q.pre_vec_mode; fp.pvG = q.pre_vG; fp.pvFS = q.pre_vFS; fp.pvS = q.pre_vS; fp.pvB = q.pre_vB;
+        if (q.pre_vec && q.pre_vec_mode == 3) fp.pvB = q.pre_vB / q.pre_vG;     // rows per clip, as in the tail
+        else if (q.pre_vec && q.pre_vec_mode == 2) fp.pvG = 1;                  // (the field is unused in mode 2: the prologue's one expression)
         fp.ln_g = (const f16*)q.ln_gamma; fp.ln_b = (const f16*)q.ln_beta; fp.ln_eps = q.ln_eps;
     } else {
         PT_CHECK(!q.ln_gamma && !q.ln_beta && !q.pre_res && !q.pre_vec, "pt_ffn_geglu_f16: ln_gamma / pre_res / pre_vec without pre_w");

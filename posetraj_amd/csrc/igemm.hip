@@ -131,7 +131,7 @@ __device__ __forceinline__ void side_targets(const pt_igemm_params& p, bool firs
     }
 }
 
-template <class CF, bool FAST>
+template <class CF, bool FAST, bool CLIP = false>   // CLIP: the instance that serves vec_mode 3 (igemm_tail.h: vec_index)
 __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TM = CF::TM, TN = CF::TN, NT = CF::NT, BM = CF::BM, BN = CF::BN;
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(CF::NT, 2) void igemm_kernel(const KParams kp) {
     }
     compute(cur);
 
-    igemm_epilogue<CF, V_RT, true>(kp, acc, smem, m0, n0, wave, lane, par);
+    igemm_epilogue<CF, V_RT, true, CLIP>(kp, acc, smem, m0, n0, wave, lane, par);
 }
 
 // ============================================================================ 256 x 256, 8-phase ping-pong main loop
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const KParams kp) {
         // loop, where every register is taken: make the lane id opaque here
         int lane_t = lane;
         asm volatile("" : "+v"(lane_t));
-        igemm_epilogue<CF, VAR, VAR == V_P0>(kp, acc, smem, m0, n0, wave, lane_t, par);
+        igemm_epilogue<CF, VAR, VAR == V_P0, false>(kp, acc, smem, m0, n0, wave, lane_t, par);
     }
     ig_stamp(kp, wave, lane, 3);
     __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));                 // no LDS-DMA may outlive the wave
@@ -645,7 +645,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
     } else {
         int lane_t = lane;                                   // (opaque: keeps the tail's lane-derived values below the K loop)
         asm volatile("" : "+v"(lane_t));
-        igemm_epilogue<CF, VAR, VAR == V_P0>(kp, acc, smem, m0, n0, wave, lane_t, par);
+        igemm_epilogue<CF, VAR, VAR == V_P0, false>(kp, acc, smem, m0, n0, wave, lane_t, par);
         ig_stamp(kp, wave, lane, 3);
         __builtin_amdgcn_s_waitcnt(pt_vmcnt(0));             // no LDS-DMA may outlive the wave
     }
@@ -653,6 +653,7 @@ __global__ __launch_bounds__(512, 2) void igemm10_kernel(const KParams kp) {
 
 
 // Second half of a split-K product: out = epilogue(sum over slabs, in slab order).  One thread per (pixel, 8 channels).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KParams kp) {
     const pt_igemm_params& p = kp.p;
     const int n8 = p.N >> 3;
@@ -706,7 +707,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const KParams kp) {
             for (int j = 0; j < 8; ++j) v[j] += r[j];
         }
         if (p.vec) {
-            const f16x8 e = *(const f16x8*)((const f16*)p.vec + (size_t)vec_index(p, m) * p.ldv + c0);
+            const f16x8 e = *(const f16x8*)((const f16*)p.vec + (size_t)(CLIP ? vec_index_clip(p, m) : vec_index(p, m)) * p.ldv + c0);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += (float)e[j];
         }
@@ -787,15 +788,25 @@ int choose_group(int tiles_m, int tiles_n, double a_bytes, double w_bytes, int c
     return best;
 }
 
-template <class CF, bool FAST>
+template <class CF, bool FAST, bool CLIP>
 void launch(const KParams& kp, hipStream_t s) {
     static bool attr_done[64] = {};                          // the opt-in is per device
     const int dev = pt_device();
     if (!attr_done[dev]) {
-        (void)hipFuncSetAttribute((const void*)igemm_kernel<CF, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
+        (void)hipFuncSetAttribute((const void*)igemm_kernel<CF, FAST, CLIP>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
         attr_done[dev] = true;
     }
-    hipLaunchKernelGGL((igemm_kernel<CF, FAST>), dim3((unsigned)(kp.tiles_m * kp.tiles_n)), dim3(CF::NT), CF::SMEM, s, kp);
+    hipLaunchKernelGGL((igemm_kernel<CF, FAST, CLIP>), dim3((unsigned)(kp.tiles_m * kp.tiles_n)), dim3(CF::NT), CF::SMEM, s, kp);
+}
+
+// vec_mode 3 never runs in a kernel that existed before it.  With its branch compiled into vec_index the tails spill more SGPRs (the
+// pipelined kernels), two plain-loop kernels move off a register cliff (256 x 256 generic K: scratch 64 -> 96 B; 256 x 32 generic K: 126
+// -> 127 VGPRs), and the clip measured 0.15 - 0.4 % slower on two boxes (profiles/r18/independent_clips.txt).  So every kernel is
+// compiled as it was, without the branch (CLIP = false), and mode 3 launches instances of its own (CLIP = true).
+template <class CF, bool FAST>
+void launch(const KParams& kp, hipStream_t s) {
+    if (kp.p.vec_mode == 3) launch<CF, FAST, true>(kp, s);
+    else                    launch<CF, FAST, false>(kp, s);
 }
 
 template <class CF>
@@ -886,7 +897,7 @@ namespace {
 // (`ws_bytes` of workspace wanted, `splits` > 1 only if the caller offered that much) and the rasterisation group.  Host only:
 // touches no device, so pt_igemm_splitk_ws_bytes and pt_igemm_plan ask it too.
 struct Plan {
-    bool fast, foldx, vec_ok;
+    bool fast, foldx, vec_ok, plain;
     int cfg, splits, gm, tiles_m, tiles_n, class_tiles;
     int64_t ws_bytes;
 };
@@ -923,6 +934,8 @@ int plan(const pt_igemm_params& p, Plan& pl) {
     }
     PT_CHECK(p.act == 0 || p.act == 2 || (p.act == 1 && p.N % 32 == 0), "pt_igemm_f16: act must be 0, 1 (GEGLU, N %% 32 == 0) or 2 (SiLU)");
     PT_CHECK(p.vec_mode == 0 || p.vec, "pt_igemm_f16: vec_mode without vec");
+    PT_CHECK(p.vec_mode != 3 || vec_clip_local_ok(p.vG, p.vFS, p.vS, p.vB),
+             "pt_igemm_f16: vec_mode 3 needs vG >= 1, vB %% vG == 0 and vFS, vS, vB > 0 (vG=%d vFS=%d vS=%d vB=%d)", p.vG, p.vFS, p.vS, p.vB);
     PT_CHECK(!(p.res_post && !p.res), "pt_igemm_f16: res_post without res");
     PT_CHECK(!(p.res_lo && !p.res), "pt_igemm_f16: res_lo without res");
     PT_CHECK(!(p.out_lo && (p.out_f32 || p.act == 1)), "pt_igemm_f16: out_lo needs an fp16, non-GEGLU output");
@@ -940,6 +953,12 @@ int plan(const pt_igemm_params& p, Plan& pl) {
     if (pl.splits > 1) cfg = 3;
     if (force < 0 && p.N <= 96 && p.act != 1 && pl.splits == 1) cfg = 5;   // tools/micro/igemm_n32_sweep.py: 2.6-4 x on N = 16 / 32, 1.5 x on 96
     if (cfg == 3 && !pl.fast) cfg = p.act == 1 ? 0 : 1;     // the 256x320 kernel has no generic-K gather
+    // vec_mode 3 runs in the plain-loop kernels only (launch<> above: instances of their own).  The pipelined kernels are compiled
+    // without it, as they were - with its branch in their tails the clip measured 0.15 - 0.4 % slower - so an un-split mode-3 launch
+    // planned for the 256 x 320 tile takes the 128 x 320 one (GEGLU: 256 x 256), and the 256 x 256 tile its plain loop.  (Split-K is
+    // unaffected: its first pass has no row vector, and the reducer has an instance for mode 3.)
+    pl.plain = p.vec && p.vec_mode == 3 && pl.splits == 1;
+    if (pl.plain && cfg == 3) cfg = p.act == 1 ? 0 : 1;
     PT_CHECK(!(cfg == 5 && p.act == 1), "pt_igemm_f16: the 256x32 configuration does not support GEGLU");
     PT_CHECK(!(cfg == 1 && p.act == 1), "pt_igemm_f16: the 128x320 configuration does not support GEGLU");
     pl.cfg = cfg;
@@ -978,6 +997,7 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
     KParams kp;
     kp.p = p;
     if (!p.vec) kp.p.vec_mode = 0;
+    if (kp.p.vec_mode == 3) kp.p.vB = p.vB / p.vG;           // the kernels take the table rows per clip (igemm_tail.h: vec_index)
     kp.zeros = (const f16*)pt_zero_page();
     kp.npad = (p.N + 127) / 128 * 128;
     kp.stamps = g_stamps; kp.stamps_cap = g_stamps_cap;
@@ -1004,9 +1024,10 @@ extern "C" int pt_igemm_f16(const pt_igemm_params* pp, void* stream) {
         const long long work = (long long)p.M * (p.N / 8);
         long long blocks = (work + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k2);
+        if (k2.p.vec_mode == 3) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, k2);
+        else                    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, k2);
     } else if (pl.cfg == 3) launch_pipelined(PIPE10, kp, s);
-    else if (pl.cfg == 0 && pl.fast) launch_pipelined(PIPE8, kp, s);
+    else if (pl.cfg == 0 && pl.fast && !pl.plain) launch_pipelined(PIPE8, kp, s);
     else if (pl.cfg == 0) launch<CfgBig, false>(kp, s);     // the plain loop for generic K
     else if (pl.cfg == 1) launch<CfgW320>(kp, pl.fast, s);
     else if (pl.cfg == 4) launch<CfgN160>(kp, pl.fast, s);

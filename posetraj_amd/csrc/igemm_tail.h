@@ -85,10 +85,25 @@ __device__ __forceinline__ int lds_khalf_off(int frow, int fq, int ks) { return 
 // reference: by value, ffn320_kernel's scalar bookkeeping - nothing else - came out re-allocated.)
 __device__ __forceinline__ int lds_wpiece_row(const int& lr) { return (lr >> 5) * 160 + ((lr >> 4) & 1) * 16 + (lr & 15); }
 
-__device__ __forceinline__ int vec_index(const pt_igemm_params& p, int m) {
+// Row of the broadcast row-vector table for output row m (vec_mode: include/posetraj_hip.h).  Mode 3, clip-local interleave: the host
+// entry points hand the kernels vB / vG, the table rows PER CLIP, in vB - one division less per row.
+// Two functions, chosen by the tail's CLIP parameter.  vec_index is the function as it was before mode 3 existed, and every kernel that
+// existed then is still compiled with it, instruction for instruction.  vec_index_clip adds mode 3's branch; it is compiled into
+// instances that only vec_mode 3 launches (igemm.hip: launch, launch_pipelined, the split-K reducer).
+// The feed-forward kernel's tail takes modes 1 and 2 only.
+__device__ __forceinline__ int vec_index(const pt_igemm_params& p, int m) {               // modes 1 and 2
     if (p.vec_mode == 1) return m / p.vG;
     return ((m / p.vFS) * p.vS + m % p.vS) % p.vB;
 }
+__device__ __forceinline__ int vec_index_clip(const pt_igemm_params& p, int m) {          // modes 1, 2 and 3
+    if (p.vec_mode == 1) return m / p.vG;
+    const int b = m / p.vFS, s = m % p.vS;
+    if (p.vec_mode != 3) return (b * p.vS + s) % p.vB;
+    const int h = b / p.vG;                                  // b = h vG + clip
+    return ((h * p.vS + s) % p.vB) * p.vG + (b - h * p.vG);
+}
+// Host: the argument rule of vec_mode 3.
+inline bool vec_clip_local_ok(int vG, int vFS, int vS, int vB) { return vG >= 1 && vFS > 0 && vS > 0 && vB > 0 && vB % vG == 0; }
 
 __device__ __forceinline__ void ig_stamp(const KParams& kp, int wave, int lane, int which) {
     if (kp.stamps && lane == 0) {
@@ -150,7 +165,7 @@ __device__ __forceinline__ void bias_init(const f16x4 (&b4)[CF::TN], f32x4 (&acc
 // normalise it read `out` alone (exactly the fp16 tensor), the epilogue that adds it as a residual reads res + res_lo
 // (side-input kind 4).  The one-rounding-per-block random walk of the stream - 0.98e-3 of the U-Net's 1.08e-3 rel-L2
 // (profiles/r02/parity_ladder*.txt) - drops to 2^-22 per store.
-template <class CF, int NTL, bool GEGLU, int NS, bool WIDE, bool FOLD = false>
+template <class CF, int NTL, bool GEGLU, int NS, bool WIDE, bool FOLD = false, bool CLIP = true>
 __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::TN][CF::TM], char* smem,
                                            int mrow0, int wcol0, int Nout, int wave, int lane, int par) {
     // (GEGLU chunks half as tall - the stores of chunk c under the GELU arithmetic of chunk c + 1 - measured +-0.5 % on both
@@ -198,7 +213,7 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                 int r, c8;
                 slot(g, r, c8);
                 const int m = min(mrow0 + rc * RH + r, p.M - 1);
-                const size_t row = skind[a] == 2 ? (size_t)vec_index(p, m) : (size_t)m;
+                const size_t row = skind[a] == 2 ? (size_t)(CLIP ? vec_index_clip(p, m) : vec_index(p, m)) : (size_t)m;
                 side[a][g] = *(const f16x8*)(sp[a] + row * sld[a] + wcol0 + c8);
             }
         }
@@ -331,7 +346,7 @@ __device__ __forceinline__ void igemm_tail(const KParams& kp, f32x4 (&acc)[CF::T
                     float rs = res ? (float)res[(size_t)m * p.ldr + col0 + j] : 0.f;
                     if (res_lo) rs += (float)res_lo[(size_t)m * p.ldr + col0 + j];
                     if (res && !res_post) x += rs;
-                    if (vec) x += (float)vec[(size_t)vec_index(p, m) * p.ldv + col0 + j];
+                    if (vec) x += (float)vec[(size_t)(CLIP ? vec_index_clip(p, m) : vec_index(p, m)) * p.ldv + col0 + j];
                     if (blend) x = alpha * (float)blend[(size_t)m * p.ldb + col0 + j] + (1.0f - alpha) * x;
                     x *= col_scale(col0);
                     if (res && res_post) x += rs;
@@ -372,7 +387,11 @@ __device__ __forceinline__ int tail_variant_dev(const pt_igemm_params& p) {
     return (p.out_lo ? V_W0 : V_P0) + nside;
 }
 
-template <class CF, int VAR, bool FOLD = false>
+// CLIP: which vec_index the tails are compiled with.  A tail without side inputs (NS = 0) has no row vector and is instantiated with
+// CLIP = false whatever the kernel asks for: the plain-loop 256 x 256 kernel and igemm8_kernel<V_P0> then share ONE instance of it, as
+// they always did - the inliner treats the tail's lambdas differently once they have a single caller, and that alone moved the
+// plain-loop kernel's register allocation.
+template <class CF, int VAR, bool FOLD = false, bool CLIP = true>
 __device__ __forceinline__ void igemm_epilogue(const KParams& kp, f32x4 (&acc)[CF::TN][CF::TM], char* smem,
                                                int m0, int n0, int wave, int lane, int par = 0) {
     constexpr int TM = CF::TM, TN = CF::TN;
@@ -392,12 +411,12 @@ __device__ __forceinline__ void igemm_epilogue(const KParams& kp, f32x4 (&acc)[C
     const int mrow0 = m0 + wr * TM * 16;
     const int var = VAR == V_RT ? tail_variant_dev(p) : VAR;
     if constexpr (TN % 2 == 0 && (VAR == V_RT || G)) {
-        if (var == V_G0)  { igemm_tail<CF, TN / 2, true, 0, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
-        if (var == V_GEW) { igemm_tail<CF, TN / 2, true, 3, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
+        if (var == V_G0)  { igemm_tail<CF, TN / 2, true, 0, false, false, false>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
+        if (var == V_GEW) { igemm_tail<CF, TN / 2, true, 3, false, false, CLIP>(kp, acc, smem, mrow0, wcol0, p.N / 2, wave, lane, par); return; }
     }
 #define PT_TAIL_CASE(V, NS_, WIDE_)                                                                                \
     if constexpr (VAR == V_RT || VAR == V)                                                                         \
-        if (var == V) { igemm_tail<CF, TN, false, NS_, WIDE_, FOLD>(kp, acc, smem, mrow0, wcol0, p.N, wave, lane, par); return; }
+        if (var == V) { igemm_tail<CF, TN, false, NS_, WIDE_, FOLD, CLIP && NS_ != 0>(kp, acc, smem, mrow0, wcol0, p.N, wave, lane, par); return; }
     PT_TAIL_CASE(V_P0, 0, false)
     PT_TAIL_CASE(V_P1, 1, false)
     PT_TAIL_CASE(V_P2, 2, false)

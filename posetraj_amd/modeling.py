@@ -233,11 +233,12 @@ class HipModel:
         self.temb_all = self._temb_stack.pack(device)
         self.xattn_all = self._xattn_stack.pack(device)
 
-    def _prologue(self, sample, timestep, encoder_hidden_states, added_time_ids, half=None):
+    def _prologue(self, sample, timestep, encoder_hidden_states, added_time_ids, half=None, independent_clips: int = 0):
         """time embeddings, stacked per-forward GEMMs, channels-last input.  Mirrors ``unet...:386-429``.
         ``half`` (pipeline-private): ``sample`` / ``added_time_ids`` hold slice ``half`` of a batch that was cut in two (the CFG
         halves, one clip each), ``encoder_hidden_states`` still holds the whole batch - the temporal cross-attention of a half
-        needs the context rows of both."""
+        needs the context rows of both.  ``independent_clips`` (pipeline / trainer-private): 0, the reference's batch, or the
+        number of clips the batch holds, halves-major, each of which then reads its own context rows only (``blocks.Ctx``)."""
         if not self._loaded:
             raise RuntimeError(f"{type(self).__name__}: no weights loaded (load_state_dict / from_pretrained / init_random_)")
         if sample.dim() != 5:
@@ -254,8 +255,10 @@ class HipModel:
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.float16).reshape(nb, -1).contiguous()
         xattn = ops.igemm(ehs, self.xattn_all) if self.xattn_all is not None else None
         if half is None:
-            ctx = B.Ctx(B=Bc, F=F, temb=temb, xattn=xattn)
+            ctx = B.Ctx(B=Bc, F=F, temb=temb, xattn=xattn, clips=int(independent_clips) or 1, independent=bool(independent_clips))
         else:
+            if independent_clips:
+                raise ValueError("independent_clips does not go with a split-CFG forward (`half`): that schedule takes one clip")
             if nb != 2 * Bc or Bc != 1:
                 raise ValueError("a half forward takes one clip of a two-row (CFG) batch")
             own = None if xattn is None else xattn[half * Bc:(half + 1) * Bc]

@@ -217,6 +217,38 @@ class StableVideoDiffusionPipelineControlNet:
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
 
+    @staticmethod
+    def _check_independent_requests(image, controlnet_condition, generator, camera_cond, latents, image_embeddings, image_latents,
+                                    num_videos_per_prompt, num_frames) -> int:
+        """The arguments of ``__call__(independent_clips=True)`` -> K, the number of requests.  Host only; every mismatch is a
+        ``ValueError`` that names the argument."""
+        if image is None and image_embeddings is not None and image_latents is not None:      # both pre-loop stages done by the caller
+            K = image_embeddings.shape[0] // 2
+        elif not isinstance(image, (list, tuple)) or len(image) == 0:
+            raise ValueError("independent_clips=True: `image` must be a list of K images, one per request")
+        else:
+            K = len(image)
+        if num_videos_per_prompt not in (None, 1):
+            raise ValueError(f"independent_clips=True: `num_videos_per_prompt` must be 1 (got {num_videos_per_prompt}); repeat the request in `image`")
+        c = controlnet_condition
+        if torch.is_tensor(c):
+            if c.dim() != 5 or c.shape[0] != K:
+                raise ValueError(f"independent_clips=True: `controlnet_condition` must be a list of {K} map sets or a [{K}, F, 3, H, W] "
+                                 f"tensor; got a tensor of shape {tuple(c.shape)}")
+        elif not isinstance(c, (list, tuple)) or len(c) != K:
+            raise ValueError(f"independent_clips=True: `controlnet_condition` must hold {K} map sets, one per image; got "
+                             f"{len(c) if isinstance(c, (list, tuple)) else type(c).__name__}")
+        if isinstance(generator, (list, tuple)) and len(generator) != K:
+            raise ValueError(f"independent_clips=True: `generator` must be one generator or a list of {K}; got a list of {len(generator)}")
+        if camera_cond is not None:
+            cam = torch.as_tensor(camera_cond)
+            if cam.dim() != 3 or tuple(cam.shape[:2]) != (K, num_frames):
+                raise ValueError(f"independent_clips=True: `camera_cond` must be [{K}, {num_frames}, 12]; got {tuple(cam.shape)}")
+        for name, t, n in (("latents", latents, K), ("image_embeddings", image_embeddings, 2 * K), ("image_latents", image_latents, 2 * K)):
+            if t is not None and t.shape[0] != n:
+                raise ValueError(f"independent_clips=True: `{name}` must have {n} rows for {K} requests (uncond halves first); got {t.shape[0]}")
+        return K
+
     def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, dtype, device, generator,
                         latents=None):
         """``pipeline...:267-299``: N(0,1) * init_noise_sigma."""
@@ -295,21 +327,23 @@ class StableVideoDiffusionPipelineControlNet:
         return video.float()
 
     # ------------------------------------------------------------------------------------------ the hot loop
-    def _networks_step(self, kind, sample, t, emb, cond, cam, ids, scale, level_w, overlap, _networks):
+    def _networks_step(self, kind, sample, t, emb, cond, cam, ids, scale, level_w, overlap, _networks, independent_clips: int = 0):
         """ControlNet + U-Net of one iteration -> fp32 channels-last prediction [2Bc, F, h, w, 4].  The zero-convs' epilogues add the
         ControlNet residuals straight into the U-Net's skips (no residual tensors, no add passes); with ``overlap`` the U-Net's encoder
         half runs beside the ControlNet on a second HIP stream.  ``kind`` "plain": ``scale`` is a scalar of those epilogues; "weighted":
-        the factors in ``level_w`` with the step's scale folded in, the scalar stays 1; "off": no ControlNet, nothing to fork or join."""
+        the factors in ``level_w`` with the step's scale folded in, the scalar stays 1; "off": no ControlNet, nothing to fork or join.
+        ``independent_clips``: 0, or the number of clips ``Bc`` when each is to read its own context rows (``denoise``)."""
         if _networks is not None:            # tools/variants/split_cfg.py: another schedule of the same two networks (A/B only)
             return _networks(self, sample, t, emb, cond, cam, ids, scale)
         unet, cn = self.unet, self.controlnet
+        ind = dict(independent_clips=independent_clips) if independent_clips else {}
         if kind == "off":
-            enc = unet._encode(sample, t, emb, ids)
+            enc = unet._encode(sample, t, emb, ids, **ind)
         else:
             if overlap and (self._side_stream is None or self._side_stream.device != sample.device):
                 self._side_stream = torch.cuda.Stream(device=sample.device)
-            enc = unet._encode_on(self._side_stream, sample, t, emb, ids) if overlap else unet._encode(sample, t, emb, ids)
-            taps, xm = cn._features(sample, t, emb, ids, cond, cam if cn.config.camera else None)
+            enc = unet._encode_on(self._side_stream, sample, t, emb, ids, **ind) if overlap else unet._encode(sample, t, emb, ids, **ind)
+            taps, xm = cn._features(sample, t, emb, ids, cond, cam if cn.config.camera else None, **ind)
             if overlap:
                 unet._join_encoded(enc, self._side_stream)
             mult = unet._multiplicity(enc, len(taps))
@@ -327,7 +361,8 @@ class StableVideoDiffusionPipelineControlNet:
                 camera_cond: Optional[torch.Tensor] = None, callback_on_step_end: Optional[Callable] = None,
                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], use_graph: bool = False,
                 overlap_streams: bool = False, _networks=None, control_guidance_start: float = 0.0,
-                control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+                control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None,
+                independent_clips: bool = False) -> torch.Tensor:
         """``pipeline...:481-583``.  ``latents`` ``[Bc, F, 4, h, w]`` already scaled by ``init_noise_sigma``;
         ``image_latents`` ``[2*Bc, 4, h, w]`` (uncond halves first, one frame - it is repeated over frames, ``:466``);
         ``image_embeddings`` ``[2*Bc, 1, D]``; ``controlnet_condition`` ``[2*Bc, F, 3, H, W]`` in [-1, 1].
@@ -345,7 +380,19 @@ class StableVideoDiffusionPipelineControlNet:
         pooled once per call); both classifier-free-guidance halves of a clip get the same weights.  Per-frame strength ``s [F]`` is
         the special case ``s[:, None, None].expand(F, h, w)``.
         A ``control_weight`` or a per-step scale sends the ControlNet steps through ``ControlNetSDVModel._accumulate_into_weighted``,
-        whose factors live in device buffers: one captured graph serves every scale and every weight map."""
+        whose factors live in device buffers: one captured graph serves every scale and every weight map.
+
+        ``independent_clips`` (a departure from the reference, made on purpose; default ``False`` = the reference's batch): like the
+        reference, a batch of ``Bc > 1`` clips is NOT ``Bc`` independent clips - the temporal blocks' cross-attention hands token
+        ``(b, f, s)`` the image context of batch element ``(b S + s) mod 2 Bc`` (``models/modified_svd.py:152-159``), so one
+        clip's video depends on another clip's image.  ``True``: every clip reads the two context rows, uncond and cond, that it reads in a
+        call of its own, in the same interleave (``vec_mode=3``, include/posetraj_hip.h) - clip ``c`` of the batch is what a one-clip call
+        computes for it, up to the summation order of batched launches; every other operator is per clip already.  Same tensors, same
+        launches but for that index; graphs of the two modes are never shared.  ``Bc = 1`` is untouched: the flag then changes no launch.
+        Not with ``_networks``.  No trained checkpoint is at hand to measure what the mode does to quality."""
+        if independent_clips and _networks is not None:
+            raise ValueError("`independent_clips` does not go with `_networks` (another schedule of the two networks, A/B only): its split-CFG "
+                             "forward takes one clip")
         plan = control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
         (Bc, F, _, h, w), dev, out_dtype = latents.shape, latents.device, latents.dtype
         control_weight = check_control_weight(control_weight, Bc, F, h, w)
@@ -385,12 +432,14 @@ class StableVideoDiffusionPipelineControlNet:
             cw = torch.ones((Bc, F, h, w), dtype=torch.float32, device=dev) if control_weight is None else control_weight.to(dev)
             level_base = pool_control_weight(cw, tap_sizes(h, w, len(self.controlnet.config.block_out_channels)))
         # One StepState per kind this call uses: with ``use_graph`` found in, or captured into, ``self._step_graphs`` under its key.
+        independent = Bc if independent_clips and Bc > 1 else 0          # one clip: the launches it always ran
         run = lambda st, sample, t_: self._networks_step(st.kind, sample, t_, st.emb, st.cond, st.cam, st.ids, controlnet_cond_scale,
-                                                         st.wbuf, overlap_streams, _networks)
+                                                         st.wbuf, overlap_streams, _networks, independent)
         geometry = GraphKey(Bc=Bc, F=F, hw=(h, w), cond_shape=tuple(cond.shape), cam_shape=None if cam is None else tuple(cam.shape),
                             kind=None, scale=None, unet=id(self.unet), controlnet=id(self.controlnet), unet_gen=self.unet._generation,
                             controlnet_gen=self.controlnet._generation, overlap=bool(overlap_streams),
-                            networks_name=getattr(_networks, '__name__', None), dispatch=ops.dispatch_key()) if use_graph else None
+                            networks_name=getattr(_networks, '__name__', None),
+                            dispatch=ops.dispatch_key() + (("independent_clips", bool(independent)),)) if use_graph else None
         live = {}
         # The sampler: a scheduler of order 2 (DPMPP2MDiscreteScheduler) takes the multistep kernel with its own host-computed
         # coefficients and one more latent-sized tensor, the previous denoised estimate; any other takes the Euler kernel.  Both run
@@ -440,7 +489,8 @@ class StableVideoDiffusionPipelineControlNet:
                  controlnet_cond_scale=1.0, batch_size=1, camera_cond=None,
                  image_embeddings: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
                  use_graph: bool = True, overlap_streams: bool = True, control_guidance_start: float = 0.0,
-                 control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None):
+                 control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None,
+                 independent_clips: bool = False):
         """Same signature as the reference (``pipeline...:316-340``; ``camera_cond`` from the ``_cam`` twin) plus
         ``image_embeddings`` ``[2,1,D]`` / ``image_latents`` ``[2,4,h,w]`` (the outputs of the CLIP / VAE-encode stages,
         ``:441,457``, for callers that have them already) and ``use_graph`` / ``overlap_streams`` (the loop as a replayed
@@ -451,9 +501,25 @@ class StableVideoDiffusionPipelineControlNet:
         Beyond the reference (see ``denoise``): ``control_guidance_start`` / ``control_guidance_end`` (diffusers' control window over
         the steps), ``controlnet_cond_scale`` as one float per step, and ``control_weight`` ``[F, h, w]`` / ``[Bc, F, h, w]`` at latent
         resolution (``h = height // 8``), intended range [0, 1] - a weight per frame and latent pixel on every ControlNet residual;
-        per-frame strength ``s [F]`` is ``s[:, None, None].expand(F, h, w)``.  They are checked before any stage runs."""
+        per-frame strength ``s [F]`` is ``s[:, None, None].expand(F, h, w)``.  They are checked before any stage runs.
+
+        ``independent_clips=True`` (see ``denoise``; NOT the reference's behaviour, default off): K requests in one call, each computed
+        as a clip of its own - what raising a batch size for throughput is expected to mean.  ``image`` is a list of K images;
+        ``controlnet_condition`` a list of K map sets or a ``[K, F, 3, H, W]`` tensor; ``generator`` one generator or a list of K (request
+        k draws its augmentation noise and its latents from generator k, as a call of its own would); ``camera_cond`` ``[K, F, 12]``;
+        ``latents`` ``[K, F, 4, h, w]``, ``image_embeddings`` ``[2K, 1, D]`` and ``image_latents`` ``[2K, 4, h, w]`` (uncond halves first)
+        when given; ``control_weight`` keeps its ``[K, F, h, w]`` form.  ``batch_size`` is taken from the list, ``num_videos_per_prompt``
+        must be 1.  ``.frames`` is a list of K clips, clip k what a call with request k alone returns (``output_type="latent"``: K tensors
+        ``[1, F, 4, h, w]``); every clip is decoded on its own.  A mismatched length is a ``ValueError`` naming the argument, raised
+        before any stage runs.  Guidance range, control scale and window are shared by the K clips."""
         num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
         control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
+        if independent_clips:
+            batch_size = self._check_independent_requests(image, controlnet_condition, generator, camera_cond, latents, image_embeddings,
+                                                          image_latents, num_videos_per_prompt, num_frames)
+            num_videos_per_prompt = 1                                                       # (None is taken as 1)
+            if isinstance(generator, tuple):                                                # randn_tensor / prepare_latents know lists
+                generator = list(generator)
         check_control_weight(control_weight, batch_size * num_videos_per_prompt, num_frames, height // self.vae_scale_factor,
                              width // self.vae_scale_factor)
         decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames                # :422
@@ -463,6 +529,8 @@ class StableVideoDiffusionPipelineControlNet:
                                       "construct the pipeline with vae=, or ask for output_type='latent'")
         dev = self.unet.device
         do_cfg = max_guidance_scale > 1.0                                                   # :438
+        if independent_clips and image is not None and all(torch.is_tensor(im) for im in image):
+            image = torch.stack([im.reshape(im.shape[-3:]) for im in image])                # K tensors [3, H, W] -> the batch tensor
         if image_embeddings is None:                                                        # :441
             if self.image_encoder is None:
                 raise NotImplementedError("no `image_encoder` was given to the pipeline: pass `image_embeddings` [2,1,D], or "
@@ -476,7 +544,10 @@ class StableVideoDiffusionPipelineControlNet:
             if self.vae is None:
                 raise NotImplementedError("no `vae` was given to the pipeline: pass `image_latents` [2,4,h,w], or construct the "
                                           "pipeline with vae= (posetraj_amd.AutoencoderKLTemporalDecoder)")
-            img = self.preprocess_condition(image, height, width)                            # image_processor.preprocess -> [-1, 1]
+            if independent_clips and torch.is_tensor(image):                                # (a tensor's range is judged per request)
+                img = torch.cat([self.preprocess_condition(im.unsqueeze(0), height, width) for im in image])
+            else:
+                img = self.preprocess_condition(image, height, width)                        # image_processor.preprocess -> [-1, 1]
             noise = randn_tensor(img.shape, generator=generator, device=img.device, dtype=img.dtype)
             img = img + noise_aug_strength * noise
             if needs_upcasting:
@@ -491,24 +562,30 @@ class StableVideoDiffusionPipelineControlNet:
         self.scheduler.set_timesteps(num_inference_steps, device=dev)                       # :482, before init_noise_sigma is read (:298)
         lat = self.prepare_latents(batch_size * num_videos_per_prompt, num_frames, self.unet.config.in_channels, height,
                                    width, image_embeddings.dtype, dev, generator, latents)
-        cond = self.preprocess_condition(controlnet_condition, height, width)               # :500
-        cond = torch.cat([cond.unsqueeze(0)] * 2)                                           # :501-503 (Q5)
+        if independent_clips:                                                               # K map sets, each prepared as a call of its own would
+            cond = torch.stack([self.preprocess_condition(c, height, width) for c in controlnet_condition])
+        else:
+            cond = self.preprocess_condition(controlnet_condition, height, width).unsqueeze(0)   # :500
+        cond = torch.cat([cond] * 2)                                                        # :501-503 (Q5)
         cam = None
         if camera_cond is not None:
-            cam = torch.as_tensor(camera_cond, dtype=torch.float32).unsqueeze(0)
-            cam = torch.cat([cam] * 2)
+            cam = torch.as_tensor(camera_cond, dtype=torch.float32)
+            cam = torch.cat([cam if independent_clips else cam.unsqueeze(0)] * 2)
         latents = self.denoise(lat, image_latents, image_embeddings, cond, num_inference_steps, min_guidance_scale,
                                max_guidance_scale, controlnet_cond_scale, cam, callback_on_step_end,
                                callback_on_step_end_tensor_inputs, use_graph=use_graph, overlap_streams=overlap_streams,
                                control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                               control_weight=control_weight)
+                               control_weight=control_weight, independent_clips=independent_clips)
         if not output_type == "latent":                                                     # :585-592
             if needs_upcasting:
                 self.vae.to(dtype=torch.float16)
-            frames = self.decode_latents(latents, num_frames, decode_chunk_size)
+            if independent_clips:                        # clip by clip: a decode chunk never spans two requests
+                frames = torch.cat([self.decode_latents(latents[k:k + 1], num_frames, decode_chunk_size) for k in range(latents.shape[0])])
+            else:
+                frames = self.decode_latents(latents, num_frames, decode_chunk_size)
             frames = tensor2vid(frames, self.image_processor, output_type=output_type)
         else:
-            frames = latents
+            frames = [latents[k:k + 1] for k in range(latents.shape[0])] if independent_clips else latents
         self.maybe_free_model_hooks()
         if not return_dict:
             return frames

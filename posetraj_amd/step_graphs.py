@@ -15,7 +15,8 @@ class GraphKey(NamedTuple):
     Bc: int; F: int; hw: tuple; cond_shape: tuple; cam_shape: Optional[tuple]                  # geometry
     kind: Optional[str]; scale: Optional[float]          # "plain" | "weighted" | "off"; the scale a plain step bakes into its epilogues, or None
     unet: int; controlnet: int; unet_gen: int; controlnet_gen: int                             # identity
-    overlap: bool; networks_name: Optional[str]; dispatch: tuple                               # ... ops.dispatch_key()
+    overlap: bool; networks_name: Optional[str]
+    dispatch: tuple      # every switch that decides which launches a step issues: ops.dispatch_key() + (("independent_clips", bool),) - denoise
 
     def geometry(self):
         return self._replace(kind=None, scale=None)

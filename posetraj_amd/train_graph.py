@@ -23,10 +23,12 @@ from .modeling import _tup
 
 
 class TrainCtx:
-    """Per-forward state: ``B`` clips of ``F`` frames; ``emb_silu`` ``[B, 4 ch0]`` and ``ehs`` ``[B, D]`` hold one row per clip."""
+    """Per-forward state: ``B`` clips of ``F`` frames; ``emb_silu`` ``[B, 4 ch0]`` and ``ehs`` ``[B, D]`` hold one row per clip.
+    ``independent`` (``ControlNetTrainer(independent_clips=True)``; not the reference's batch): the temporal blocks' cross-attention gives
+    every clip its own context row instead of the batch-wide interleave."""
 
-    def __init__(self, F: int, emb_silu: Var, ehs: Var, B: int = 1):
-        self.B, self.F, self.emb_silu, self.ehs = B, F, emb_silu, ehs
+    def __init__(self, F: int, emb_silu: Var, ehs: Var, B: int = 1, independent: bool = False):
+        self.B, self.F, self.emb_silu, self.ehs, self.independent = B, F, emb_silu, ehs, bool(independent)
 
 
 class ResBlock:
@@ -110,7 +112,8 @@ class Transformer:
             u = AD.dense(tape, a, L.to, res=u)
             xa = AD.dense(tape, AD.dense(tape, ctx.ehs, L.txv), L.txo)
             # a batch's temporal context is built [H W, B]-major against [B, H W]-major tokens: row (b F + f) S + s gets clip (b S + s) mod B
-            u = AD.add_rowvec(tape, u, xa, F * S) if B == 1 else AD.add_rowvec_interleaved(tape, u, xa, B, F, S)
+            # - unless the clips are independent: then, as for one clip, every row of clip b gets clip b's
+            u = AD.add_rowvec(tape, u, xa, F * S) if B == 1 or ctx.independent else AD.add_rowvec_interleaved(tape, u, xa, B, F, S)
             u = ff(AD.layernorm(tape, u, L.tln3), L.tf1, L.tf2, u)
             h = AD.blend(tape, hs, u, self.mix)
         return AD.dense(tape, h, self.proj_out, res=x)
@@ -187,17 +190,18 @@ class ControlNetGraph:
         self.zero_mid = zc("controlnet_mid_block")
 
     def run(self, tape: Tape, sample_cl: torch.Tensor, geom, timestep, ehs: torch.Tensor, added_time_ids, cond: torch.Tensor,
-            conditioning_scale: float = 1.0, camera_cond: Optional[torch.Tensor] = None, checkpoint: bool = False):
+            conditioning_scale: float = 1.0, camera_cond: Optional[torch.Tensor] = None, checkpoint: bool = False,
+            independent_clips: bool = False):
         """``sample_cl``: the network input channels-last ``[B F h w, 8]``, ``geom`` = ``(B F, h, w)``; ``ehs``: ``[B, D]``; ``cond``:
         ``[B F, 3, H, W]`` trajectory maps; ``camera_cond``: ``[B F, 12]`` (R|T per frame) for the camera twin.  ``B`` is the number of
         rows of ``ehs``.  ``checkpoint``: every residual block and every transformer is a checkpointed segment
-        (``controlnet.enable_gradient_checkpointing()``)."""
+        (``controlnet.enable_gradient_checkpointing()``).  ``independent_clips``: ``TrainCtx.independent``."""
         N, h, w = geom
         dev = sample_cl.device
         B = ehs.shape[0]
         if N % B:
             raise ValueError(f"ControlNetGraph.run: {N} frames do not divide into {B} clips")
-        ctx = TrainCtx(N // B, self.time.run(tape, timestep, added_time_ids, dev), Var(ehs, need=False), B)
+        ctx = TrainCtx(N // B, self.time.run(tape, timestep, added_time_ids, dev), Var(ehs, need=False), B, independent_clips)
         Fc, Cc, H, W = cond.shape
         c = Var(ops.to_channels_last(cond, cpad=8).view(Fc * H * W, 8), need=False)
         c = AD.silu(tape, AD.dense(tape, c, self.ce_in, geom=(Fc, H, W)))
@@ -257,11 +261,12 @@ class UNetDecoderGraph:
         self.conv_out = Dense(P, "conv_out.weight", "conv_out.bias", kind="conv", padding=1)
 
     def run(self, tape: Tape, state: dict, mult: List[int], residuals: List[Var], mid_residual: Var, emb_silu: torch.Tensor, ehs: torch.Tensor,
-            checkpoint: bool = False) -> Var:
+            checkpoint: bool = False, independent_clips: bool = False) -> Var:
         """``state``: what ``UNetSpatioTemporalConditionControlNetModel._encode`` returned (inference kernels).  ``checkpoint``: every
-        residual block (two-source: it closes over its skip) and every transformer is a checkpointed segment."""
+        residual block (two-source: it closes over its skip) and every transformer is a checkpointed segment.  ``independent_clips``:
+        ``TrainCtx.independent`` (the encoder that made ``state`` must have run in the same mode)."""
         Bc, F = state["dims"]
-        ctx = TrainCtx(F, Var(emb_silu, need=False), Var(ehs, need=False), Bc)
+        ctx = TrainCtx(F, Var(emb_silu, need=False), Var(ehs, need=False), Bc, independent_clips)
         skips = []
         for s, r, m in zip(state["skips"], residuals, mult):
             n, hh, ww, c = s.shape

@@ -304,6 +304,13 @@ class ControlNetTrainer:
     mode above works on a batch without code of its own, ``deterministic`` included (the new reduction has its two-launch form);
     ``use_graph=True`` refuses a batch with a ``ValueError``.  What a batch buys at 14 x 320 x 576: DESIGN 4.13.
 
+    ``independent_clips`` (default ``False`` = the reference's batch, launch for launch): ``True`` departs from the reference on purpose
+    and gives a batch the standard meaning - every clip's temporal cross-attention reads that clip's own context (``autodiff.add_rowvec``,
+    one row per clip, the op ``B == 1`` uses, on both tapes; ``vec_mode=3`` in the frozen encoder's inference kernels), so a batch of
+    ``B`` clips is the mean of ``B`` one-clip steps: losses and gradients equal those of ``B`` accumulated micro-batches up to rounding.
+    ``B == 1`` is untouched.  Every mode above works as it does on a batch; ``use_graph=True`` still refuses a batch; a checkpoint file
+    knows nothing of the flag.  What the mode does to a trained model's quality has not been measured (no trained checkpoint at hand).
+
     ``unet`` must have been loaded with ``keep_source=True`` (its up-path weights are re-packed for the data gradients).
     ``controlnet_state_dict``: the parameters to train, e.g. ``ControlNetSDVModel.from_unet(unet).state_dict()`` (``:935-938``)."""
 
@@ -315,7 +322,7 @@ class ControlNetTrainer:
                  lr_scheduler=None, use_graph: bool = False, device_scalars: Optional[bool] = None, encoder_stream: bool = True,
                  pack_stream: bool = True, use_ema: bool = False, ema_decay: float = 0.9999, ema_min_decay: float = 0.0,
                  ema_update_after_step: int = 0, use_ema_warmup: bool = False, ema_inv_gamma: float = 1.0, ema_power: float = 2 / 3,
-                 use_8bit_adam: bool = False, gradient_checkpointing=False, deterministic: bool = False):
+                 use_8bit_adam: bool = False, gradient_checkpointing=False, deterministic: bool = False, independent_clips: bool = False):
         from . import autodiff as AD
         from . import grad_sync
         from . import train_graph as TG
@@ -332,6 +339,7 @@ class ControlNetTrainer:
             raise ValueError("ControlNetTrainer(use_graph=True) does not take deterministic=True: the deterministic reductions take a workspace "
                              "per call from the allocator of the calling stream, and the captured step is out of the mode's scope")
         self.gradient_checkpointing = gradient_checkpointing
+        self.independent_clips = bool(independent_clips)
         self._ckpt_cn, self._ckpt_dec = bool(gradient_checkpointing), gradient_checkpointing == "all"
         cfg = dict(controlnet_config)
         self.unet, self.device, self.config = unet, dev, cfg
@@ -500,6 +508,11 @@ class ControlNetTrainer:
         # depends on the temporal pass nowhere between the ControlNet's outputs and the join of the residual gradients: it runs on
         # a stream of its own beside the temporal pass, forward and backward.
         tape_cn, tape, tape_sp = AD.Tape(), AD.Tape(), AD.Tape()
+        # independent_clips on a batch: the frozen encoder (inference kernels: vec_mode 3 over B rows, no CFG halves) and the two tapes
+        # (add_rowvec, one row per clip) give every clip its own temporal context; B = 1 and the default add no argument to any call
+        ind = self.independent_clips and B > 1
+        ind_enc = dict(independent_clips=B) if ind else {}
+        ind_tape = dict(independent_clips=True) if ind else {}
         cam = I.get("cam")
         main = torch.cuda.current_stream()
         # the frozen U-Net's encoder half (inference kernels, no tape) depends on the ControlNet nowhere: it runs on a stream of its own
@@ -510,7 +523,7 @@ class ControlNetTrainer:
             if self._enc_stream is None:
                 self._enc_stream = torch.cuda.Stream()
             with torch.no_grad():
-                state = unet._encode_on(self._enc_stream, inp, timesteps, I["ehs"], ids)
+                state = unet._encode_on(self._enc_stream, inp, timesteps, I["ehs"], ids, **ind_enc)
         if "traj" not in I:                                   # staged here, behind the encoder's launches: the device is busy meanwhile
             I["traj"] = I.pop("traj_src").to(dev, torch.float16)
         if self._packs_pending:                               # the packs re-written behind the last optimizer step (their own stream)
@@ -518,7 +531,7 @@ class ControlNetTrainer:
             self._packs_pending = False
         traj = I["traj"][0] if B == 1 else I["traj"].reshape((B * F,) + tuple(I["traj"].shape[2:]))
         outs, mid = self.controlnet.run(tape_cn, I["x"].view(B * F * h * w, 8), (B * F, h, w), timesteps, ehs16, ids, traj, camera_cond=cam,
-                                        checkpoint=self._ckpt_cn)
+                                        checkpoint=self._ckpt_cn, **ind_tape)
         with torch.no_grad():
             emb_silu = unet.time.run(timesteps, ids, B)
 
@@ -545,7 +558,7 @@ class ControlNetTrainer:
                 spatial_stream.wait_stream(main)                                                # ControlNet outputs, emb_silu, inputs
             with torch.cuda.stream(spatial_stream) if spatial_stream is not None else _null():
                 with torch.no_grad():
-                    state_s = unet._encode(inp[:, ran_idx].unsqueeze(1), timesteps, I["ehs"], ids)
+                    state_s = unet._encode(inp[:, ran_idx].unsqueeze(1), timesteps, I["ehs"], ids, **ind_enc)
                 mult_s = unet._multiplicity(state_s, len(outs))
                 def frame(o):                                # clip b's own rows of frame ran_idx, b = 0 .. B - 1 (a batch of B one-frame clips)
                     n = o.v.shape[0] // (B * F)
@@ -554,15 +567,15 @@ class ControlNetTrainer:
 
                 res_s = [frame(o) for o in outs]
                 mid_s = frame(mid)
-                pred_s = self.decoder.run(tape_sp, state_s, mult_s, res_s, mid_s, emb_silu, ehs16, checkpoint=self._ckpt_dec)
+                pred_s = self.decoder.run(tape_sp, state_s, mult_s, res_s, mid_s, emb_silu, ehs16, checkpoint=self._ckpt_dec, **ind_tape)
                 ls = loss_of(pred_s, noisy[:, ran_idx:ran_idx + 1].contiguous(), lat[:, ran_idx:ran_idx + 1].contiguous(), 1, 0.5)
         if state is None:
             with torch.no_grad():
-                state = unet._encode(inp, timesteps, I["ehs"], ids)
+                state = unet._encode(inp, timesteps, I["ehs"], ids, **ind_enc)
         else:
             unet._join_encoded(state, self._enc_stream)
         mult = unet._multiplicity(state, len(outs))
-        pred = self.decoder.run(tape, state, mult, outs, mid, emb_silu, ehs16, checkpoint=self._ckpt_dec)
+        pred = self.decoder.run(tape, state, mult, outs, mid, emb_silu, ehs16, checkpoint=self._ckpt_dec, **ind_tape)
         lt = loss_of(pred, noisy, lat, F, 1.0)
         sync = self._micro + 1 >= self.accumulation          # inside an accumulation cycle only the last micro-batch synchronises
         if sync:

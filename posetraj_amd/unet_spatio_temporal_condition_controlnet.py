@@ -83,11 +83,11 @@ class UNetSpatioTemporalConditionControlNetModel(HipModel):
     # the collected skips and to the mid block's output (:451-469) - so it is independent of the ControlNet forward:
     # the pipeline and the trainer run the two concurrently on two HIP streams (two branches of a captured hipGraph): same kernels,
     # same results, the two streams' workgroups fill each other's tail rounds and memory-bound phases.
-    def _encode_on(self, side, *args):
-        """Fork: ``_encode(*args)`` on the stream ``side``, behind what the current stream holds so far."""
+    def _encode_on(self, side, *args, **kwargs):
+        """Fork: ``_encode(*args, **kwargs)`` on the stream ``side``, behind what the current stream holds so far."""
         side.wait_stream(torch.cuda.current_stream(side.device))
         with torch.cuda.stream(side):
-            return self._encode(*args)
+            return self._encode(*args, **kwargs)
 
     @staticmethod
     def _join_encoded(state, side):
@@ -99,8 +99,10 @@ class UNetSpatioTemporalConditionControlNetModel(HipModel):
                 if part is not None:
                     part.record_stream(main)
 
-    def _encode(self, sample, timestep, encoder_hidden_states, added_time_ids, half=None):
-        ctx, x, (Bc, F, h, w) = self._prologue(sample, timestep, encoder_hidden_states, added_time_ids, half=half)
+    def _encode(self, sample, timestep, encoder_hidden_states, added_time_ids, half=None, independent_clips: int = 0):
+        """``independent_clips``: see ``_prologue``; the state carries it to ``_decode`` in its ``ctx``."""
+        ctx, x, (Bc, F, h, w) = self._prologue(sample, timestep, encoder_hidden_states, added_time_ids, half=half,
+                                               independent_clips=independent_clips)
         N = Bc * F
         x = ops.igemm(x, self.conv_in, geom=(N, h, w)).view(N, h, w, -1)
         skips = [x]
