@@ -5,6 +5,7 @@
 #include "pt_common.h"
 #include "../../include/posetraj_batch.h"
 #include "pt_fold.h"
+#include "pt_launch.h"
 
 namespace {
 
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void add_rowvec_interleaved_kernel(const f16* 
 // out[j, c] += sum over {r : j(r) = j} of dy[r, c].  Class j is {(b, s) : b S + s = j + k B, k = 0 .. S - 1} x all frames: exactly
 // F S rows, enumerated t = f S + k -> q = j + k B, b = q / S, s = q % S, r = (b F + f) S + s.  grid (slabs over t, strips of 256
 // channels, B): every row of dy is read by exactly one workgroup, as whole 16-byte chunks.  Written like colsum_kernel
-// (backward.hip).  DET: out is the workspace, part[slab][j][C].
+// (norm_bwd.hip).  DET: out is the workspace, part[slab][j][C].
 template <bool DET>
 __global__ __launch_bounds__(256) void colsum_interleaved_kernel(const f16* __restrict__ dy, uint32_t F, uint32_t S, uint32_t B, int rows_per_slab,
                                                                  int C, float* __restrict__ out) {
@@ -95,15 +96,6 @@ __global__ __launch_bounds__(256) void colsum_interleaved_kernel(const f16* __re
     }
 }
 
-// ~4096 workgroups in total, at least 64 rows per slab, a multiple of TY (backward.hip: slab_rows)
-inline int slab_rows(int64_t rows, int64_t other_blocks) {
-    int64_t slabs = 4096 / (other_blocks > 0 ? other_blocks : 1);
-    if (slabs < 1) slabs = 1;
-    int64_t rps = (rows + slabs - 1) / slabs;
-    if (rps < 64) rps = 64;
-    return (int)((rps + TY - 1) / TY * TY);
-}
-
 inline bool sizes_ok(int32_t B, int32_t F, int32_t S, int32_t Cc) {
     return B > 0 && B < 65536 && F > 0 && S > 0 && Cc > 0 && Cc % 8 == 0 && (int64_t)B * F * S * (Cc / 8) < ((int64_t)1 << 31);
 }
@@ -130,14 +122,13 @@ static int colsum_interleaved_launch(const char* who, bool det, const void* dy, 
     PT_CHECK(sizes_ok(B, F, S, Cc), "%s: bad sizes (B=%d F=%d S=%d C=%d: C %% 8 == 0, B F S C / 8 < 2^31)", who, B, F, S, Cc);
     const int strips = (Cc + 255) / 256;
     const int64_t FS = (int64_t)F * S;
-    const int rps = slab_rows(FS, (int64_t)strips * B);
+    const int rps = slab_rows(FS, (int64_t)strips * B, TY);
     const int slabs = (int)((FS + rps - 1) / rps);
     const dim3 grid(slabs, strips, B);
     hipStream_t s = (hipStream_t)stream;
     if (det) {
         const int64_t n = (int64_t)B * Cc;
-        PT_CHECK(ws && ((uintptr_t)ws & 3) == 0 && ws_floats >= slabs * n, "%s: the workspace holds %lld floats, %lld needed", who,
-                 (long long)(ws ? ws_floats : 0), (long long)(slabs * n));
+        PT_CHECK_WS(who, ws, ws_floats, slabs * n);
         hipLaunchKernelGGL(colsum_interleaved_kernel<true>, grid, dim3(256), 0, s, (const f16*)dy, (uint32_t)F, (uint32_t)S, (uint32_t)B, rps, Cc, ws);
         launch_fold<float>(s, fold_job(ws, n, slabs, out, 1));
     } else {
@@ -154,7 +145,7 @@ extern "C" int ptb_colsum_interleaved_f16(const void* dy, int32_t B, int32_t F, 
 extern "C" int64_t ptb_colsum_interleaved_ws_floats(int32_t B, int32_t F, int32_t S, int32_t Cc) {
     if (!sizes_ok(B, F, S, Cc)) return 0;
     const int64_t FS = (int64_t)F * S;
-    const int rps = slab_rows(FS, (int64_t)((Cc + 255) / 256) * B);
+    const int rps = slab_rows(FS, (int64_t)((Cc + 255) / 256) * B, TY);
     return (FS + rps - 1) / rps * B * Cc;
 }
 

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/posetraj_hip.h"
 
@@ -52,6 +53,17 @@ void pt_prof_end(int family, hipStream_t s);
 __device__ __forceinline__ float pt_silu(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
+
+// d silu(z) / dz of the training step's reverse pass (GroupNorm + SiLU backward, pt_silu_bwd), IEEE division
+__device__ __forceinline__ float pt_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float pt_dsilu(float z) { const float s = pt_sigmoid(z); return s * (1.0f + z * (1.0f - s)); }
+
+// A scalar that a kernel takes as a launch argument or (DEV) from device memory, read once before its loop: a captured launch
+// (the training step as a hipGraph) cannot take a host float that changes every step.  pt_scalar_arg<DEV> is the parameter's type
+// (`__restrict__` like the kernel's other pointers: without it lerp_kernel<true> compiles to a different instruction stream).
+template <bool DEV> using pt_scalar_arg = std::conditional_t<DEV, const float* __restrict__, float>;
+__device__ __forceinline__ float pt_scalar(float v) { return v; }
+__device__ __forceinline__ float pt_scalar(const float* p) { return *p; }
 
 // erf-GELU.  With z = |x| / sqrt(2):  gelu(x) = x * Phi(x) = relu(x) - (|x| / 2) * erfc(z), and
 //   erfc(z) ~= 2^(-z (c1 + c2 z + c3 z^2 + c4 z^3 + c5 z^4))

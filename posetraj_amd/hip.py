@@ -14,8 +14,8 @@ import typing
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.abspath(os.environ["PT_LIB"]) if os.environ.get("PT_LIB") else os.path.join(HERE, "libposetraj_hip.so")   # PT_LIB: A/B against another build on one box
-SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "backward.hip", "attn_bwd.hip", "batch.hip", "control.hip", "sampler.hip"]
-HEADERS = ["pt_common.h", "igemm_tail.h", "pt_fold.h"]
+SOURCES = ["api.hip", "igemm.hip", "ffn.hip", "lnlin.hip", "norm.hip", "attn.hip", "attn_general.hip", "elementwise.hip", "vae.hip", "vae_f32.hip", "clip.hip", "raster.hip", "train.hip", "gemm.hip", "norm_bwd.hip", "pointwise_bwd.hip", "optim.hip", "attn_bwd.hip", "batch.hip", "control.hip", "sampler.hip"]
+HEADERS = ["pt_common.h", "igemm_tail.h", "pt_fold.h", "pt_launch.h"]
 INCLUDE = os.path.join(HERE, "..", "include")
 
 

@@ -1,4 +1,4 @@
-"""SURVEY 8(f)4 on the MI355X: the training step's reverse pass - pt_gemm_f16, the kernels of csrc/backward.hip, the tape
+"""SURVEY 8(f)4 on the MI355X: the training step's reverse pass - pt_gemm_f16, the kernels of csrc/norm_bwd.hip, pointwise_bwd.hip and optim.hip, the tape
 primitives of posetraj_amd/autodiff.py and ControlNetTrainer - through the C ABI against torch autograd on the CPU (fp32, over
 the same fp16-representable inputs) and against the reference-run fixture tests/golden/train_grads.npz.
 
@@ -281,6 +281,23 @@ def test_blend_with_the_weight_in_device_memory(dev, AD, blend_case, monkeypatch
     print("blend, device scalars: forward %.2e, da %.2e, db %.2e, dmix %.2e" % got)
     assert got[0] < 6e-4 and got[1] < 6e-4 and got[2] < 6e-4 and got[3] < 1e-3
     assert o.g is None
+
+
+def test_lerp_host_and_device_alpha_agree_bit_for_bit(dev):
+    """pt_lerp_f16 (alpha a launch argument) and pt_lerp_f16_dev (the same fp32 value in device memory) are two instances of one
+    kernel body: identical outputs.  n: one 8-element chunk; 257 chunks (a second block with one live lane); the AlphaBlender's."""
+    from posetraj_amd import hip, ops
+    L, st = hip.lib(), ops._stream()
+    for n in (8, 8 * 257, 8 * 3840):
+        a, b = h16(n, seed=31).to(dev), h16(n, seed=32).to(dev)
+        for alpha in (0.0, 0.3, 1.0):
+            alpha_dev = torch.tensor([alpha], dtype=torch.float32, device=dev)
+            host, devm = (torch.full((n,), float("nan"), dtype=torch.float16, device=dev) for _ in range(2))
+            hip.check(L.pt_lerp_f16(a.data_ptr(), b.data_ptr(), alpha, n, host.data_ptr(), st))
+            hip.check(L.pt_lerp_f16_dev(a.data_ptr(), b.data_ptr(), alpha_dev.data_ptr(), n, devm.data_ptr(), st))
+            assert torch.equal(host.view(torch.int16), devm.view(torch.int16)), (n, alpha)
+            al = float(alpha_dev.item())
+            assert rel(host, al * a.float() + (1.0 - al) * b.float()) < 5e-4, (n, alpha)
 
 
 def test_blend_over_a_frozen_store(dev, AD, blend_case, monkeypatch):
