@@ -46,13 +46,19 @@ _ROWS = (
     Abi("sampler", "posetraj_sampler.h", "pts_", "PT_SAMPLER_ABI_VERSION", {}),      # the linear multistep (DPM-Solver++(2M)) step
 )
 
-_lib = _checked = None
+# The windowed denoise loop's two passes are an add-on library of their own (posetraj_amd/windows.py binds it): libposetraj_window.so
+# from csrc/window.hip, declared in include/posetraj_window.h.  Not a row of the table above, not in SOURCES or header_paths(): the main
+# library, its digest and its rebuild inputs do not know it.  The same reader reads its header; build() makes it after the main link.
+_WINDOW_ROW = Abi("window", "posetraj_window.h", "ptw_", "PT_WINDOW_ABI_VERSION", {})
+WINDOW_SOURCE, WINDOW_LIB_PATH = "window.hip", os.path.join(HERE, "libposetraj_window.so")
+
+_lib = _checked = _window = None
 
 # The headers are the only description of the ABI: the parameter structs, the signature tables and the versions below are
 # read from them at import (the C subset they use, nothing more; tests/test_abi_cpu.py has a C++ compiler confirm the reading).
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _TYPE = r"(?:const\s+)?\w+\s*\*?"
-_ENTRY = r"(?:%s)[a-z0-9_]+" % "|".join(re.escape(a.prefix) for a in _ROWS)
+_ENTRY = r"(?:%s)[a-z0-9_]+" % "|".join(re.escape(a.prefix) for a in _ROWS + (_WINDOW_ROW,))
 _DECL = re.compile(r"""\s*(?: typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P=tag)\s*;
                             | (?P<ret>%s)\s*\b(?P<fn>%s)\s*\((?P<params>[^()]*)\)\s*;
                             | extern\s+"C"\s*\{ | \} )""" % (_TYPE, _ENTRY), re.X)
@@ -122,6 +128,8 @@ for _abi in _ROWS:
     with open(os.path.join(INCLUDE, _abi.header)) as _f:
         ABIS[_abi.name] = _parse_header(_f.read(), _abi, {tag: cls for row in ABIS.values() for tag, cls in row.structs.items()})
     globals().update({cls.__name__: cls for cls in ABIS[_abi.name].structs.values()})       # IgemmParams ... GemmParams, Adam8Segment
+with open(os.path.join(INCLUDE, _WINDOW_ROW.header)) as _f:
+    WINDOW_ABI = _parse_header(_f.read(), _WINDOW_ROW, {})                                   # the add-on library's row, read the same way
 # the core header's values under the names they have always had
 _abi = ABIS["core"]
 HEADER, STRUCT_CLASSES, ABI_VERSION, PROTOTYPES, SIGNATURES = os.path.join(INCLUDE, _abi.header), _abi.struct_classes, _abi.version, _abi.prototypes, _abi.signatures
@@ -135,7 +143,7 @@ def header_paths() -> list:
 def build(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 -> posetraj_amd/libposetraj_hip.so (cross-compiles without a GPU).  One object per
     source under ``csrc/_obj`` (re-compiled only when the source or a header is newer; up to 8 compiles in parallel, largest file first), then
-    one link.  Refuses to run while ``PT_LIB`` points the loader at another library (an A/B build must not be overwritten
+    one link; then the add-on library ``libposetraj_window.so`` from ``csrc/window.hip`` by the same rule.  Refuses to run while ``PT_LIB`` points the loader at another library (an A/B build must not be overwritten
     by a build of the current tree)."""
     if os.environ.get("PT_LIB"):
         raise RuntimeError("posetraj_amd.hip.build: PT_LIB is set (A/B against another library); unset it to build the tree's own")
@@ -185,6 +193,18 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if r.returncode != 0:
             raise RuntimeError(f"hipcc link failed ({r.returncode}):\n{r.stderr[-4000:]}")
         _write_resource_report("\n".join(open(o + ".remarks").read() for o in objs))
+    # the add-on library of the windowed loop: same flags, same object directory, its source and its header its own rebuild inputs
+    src, obj = os.path.join(CSRC, WINDOW_SOURCE), os.path.join(objdir, WINDOW_SOURCE + ".o")
+    inputs = [src, os.path.join(INCLUDE, _WINDOW_ROW.header), os.path.join(CSRC, "pt_common.h"), os.path.join(INCLUDE, ABIS["core"].header)]
+    if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(i) for i in inputs):
+        compile_one((src, obj, obj + ".remarks"))
+    if not os.path.exists(WINDOW_LIB_PATH) or os.path.getmtime(WINDOW_LIB_PATH) < os.path.getmtime(obj):
+        cmd = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", WINDOW_LIB_PATH, obj]
+        if verbose:
+            print(" ".join(cmd))
+        r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc link failed ({r.returncode}):\n{r.stderr[-4000:]}")
     return LIB_PATH
 
 
@@ -260,6 +280,32 @@ def checked():
     if _checked is None:
         _checked = _load(_raise_on_status)
     return _checked
+
+
+def window():
+    """The add-on library of the windowed denoise loop (include/posetraj_window.h), checked: a status-returning entry point raises
+    ``RuntimeError`` with the library's own message on a non-zero status.  Raises if it has not been built or is of another version."""
+    global _window
+    if _window is None:
+        if not os.path.exists(WINDOW_LIB_PATH):
+            raise RuntimeError(f"{WINDOW_LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(posetraj_amd has no CPU or PyTorch fallback path)")
+        L, abi = C.CDLL(WINDOW_LIB_PATH), WINDOW_ABI
+
+        def raise_on_status(rc, fn, args):
+            if rc != 0:
+                raise RuntimeError(f"libposetraj_window: {fn.__name__} failed ({rc}): {L.ptw_last_error().decode()}")
+            return rc
+
+        for name, (res, args) in abi.signatures.items():
+            fn = getattr(L, name)            # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+            if abi.prototypes[name][0] == "int" and name != abi.prefix + "abi_version":
+                fn.errcheck = raise_on_status
+        if L.ptw_abi_version() != abi.version:
+            raise RuntimeError(f"libposetraj_window.so ABI version {L.ptw_abi_version()} differs from the header's {abi.version}; rebuild")
+        _window = L
+    return _window
 
 
 def _raise_on_status(rc, fn, args):

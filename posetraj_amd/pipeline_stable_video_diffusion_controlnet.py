@@ -362,7 +362,8 @@ class StableVideoDiffusionPipelineControlNet:
                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], use_graph: bool = False,
                 overlap_streams: bool = False, _networks=None, control_guidance_start: float = 0.0,
                 control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None,
-                independent_clips: bool = False) -> torch.Tensor:
+                independent_clips: bool = False, window_frames: Optional[int] = None, window_stride: Optional[int] = None,
+                window_batch: Optional[int] = None) -> torch.Tensor:
         """``pipeline...:481-583``.  ``latents`` ``[Bc, F, 4, h, w]`` already scaled by ``init_noise_sigma``;
         ``image_latents`` ``[2*Bc, 4, h, w]`` (uncond halves first, one frame - it is repeated over frames, ``:466``);
         ``image_embeddings`` ``[2*Bc, 1, D]``; ``controlnet_condition`` ``[2*Bc, F, 3, H, W]`` in [-1, 1].
@@ -389,10 +390,33 @@ class StableVideoDiffusionPipelineControlNet:
         call of its own, in the same interleave (``vec_mode=3``, include/posetraj_hip.h) - clip ``c`` of the batch is what a one-clip call
         computes for it, up to the summation order of batched launches; every other operator is per clip already.  Same tensors, same
         launches but for that index; graphs of the two modes are never shared.  ``Bc = 1`` is untouched: the flag then changes no launch.
-        Not with ``_networks``.  No trained checkpoint is at hand to measure what the mode does to quality."""
+        Not with ``_networks``.  No trained checkpoint is at hand to measure what the mode does to quality.
+
+        ``window_frames`` (beyond the reference; default ``None`` = this loop as it always ran, launch for launch): a long video from a
+        short-clip model.  ``latents`` is ONE request ``[1, Ft, 4, h, w]``; it is denoised as ``K`` overlapping windows of
+        ``window_frames`` frames, ``window_stride`` apart (default ``window_frames // 2``; the last window ends on the last frame -
+        ``posetraj_amd.windows.window_plan``), each window one ordinary clip evaluation on the slices a call on that window would get
+        (``controlnet_condition [2, Ft, 3, H, W]``, ``camera_cond [2, Ft, 12]``, ``control_weight [Ft, h, w]``) with the request's own
+        image latents, embedding and time ids; the guidance ramp runs over the frames of a window.  At every step the predictions of the
+        windows that cover a frame are blended with normalised triangular weights, and the blended prediction takes the scheduler's
+        step.  ``window_batch`` windows (a divisor of K; default K) go through the networks per evaluation as independent clips - the
+        captured graph is that of an ``independent_clips`` batch of ``window_batch`` clips of ``window_frames`` frames, shared by all
+        groups; fewer windows per evaluation save memory and reload each group's condition every step.  Every window is conditioned on
+        the same first image.  Not with ``independent_clips`` or ``_networks``; a refusal is a ``ValueError`` naming the argument.  No
+        trained checkpoint is at hand to measure quality."""
         if independent_clips and _networks is not None:
             raise ValueError("`independent_clips` does not go with `_networks` (another schedule of the two networks, A/B only): its split-CFG "
                              "forward takes one clip")
+        if window_frames is None:
+            if window_stride is not None or window_batch is not None:
+                raise ValueError("`window_stride` / `window_batch` need `window_frames` (the windowed loop is off without it)")
+        else:
+            if independent_clips or _networks is not None:
+                raise ValueError("`window_frames` serves one request through the loop's own networks: it does not go with "
+                                 f"`{'independent_clips' if independent_clips else '_networks'}`")
+            return self._denoise_windows(latents, image_latents, image_embeddings, controlnet_condition, num_inference_steps, min_guidance_scale,
+                                         max_guidance_scale, controlnet_cond_scale, camera_cond, callback_on_step_end, use_graph, overlap_streams,
+                                         control_guidance_start, control_guidance_end, control_weight, window_frames, window_stride, window_batch)
         plan = control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
         (Bc, F, _, h, w), dev, out_dtype = latents.shape, latents.device, latents.dtype
         control_weight = check_control_weight(control_weight, Bc, F, h, w)
@@ -478,6 +502,115 @@ class StableVideoDiffusionPipelineControlNet:
                     x = new.to(torch.float32).contiguous().clone()
         return x.to(out_dtype)
 
+    def _denoise_windows(self, latents, image_latents, image_embeddings, controlnet_condition, num_inference_steps, min_guidance_scale,
+                         max_guidance_scale, controlnet_cond_scale, camera_cond, callback_on_step_end, use_graph, overlap_streams,
+                         control_guidance_start, control_guidance_end, control_weight, window_frames, window_stride, window_batch):
+        """``denoise(window_frames=...)``.  Per step and group of ``G = window_batch`` windows: the window prologue into the
+        state's input, the networks as ``G`` independent clips of ``Fw`` frames (the state, key and graph of such a batch); then, once
+        per step, guidance + blend of the K predictions into one ``[Ft, 4, h, w]`` prediction and the scheduler's flat step kernel."""
+        from . import windows as W
+        if latents.dim() != 5 or latents.shape[0] != 1:
+            raise ValueError(f"`window_frames` serves one request: `latents` must be [1, num_frames, 4, h, w]; got {tuple(latents.shape)}")
+        (_, Ft, _, h, w), dev, out_dtype = latents.shape, latents.device, latents.dtype
+        wplan, G = W.resolve(Ft, window_frames, window_stride, window_batch)
+        K, Fw, groups = wplan.K, wplan.window_frames, wplan.K // G
+        for name, t, want in (("image_latents", image_latents, (2,)), ("image_embeddings", image_embeddings, (2,)),
+                              ("controlnet_condition", controlnet_condition, (2, Ft)), ("camera_cond", camera_cond, (2, Ft))):
+            if t is not None and tuple(t.shape[:len(want)]) != want:
+                raise ValueError(f"`window_frames` serves one request of {Ft} frames: `{name}` must begin {list(want)} (uncond half first); "
+                                 f"got {tuple(t.shape)}")
+        plan = control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
+        control_weight = check_control_weight(control_weight, 1, Ft, h, w)
+        weighted = control_weight is not None or is_scale_sequence(controlnet_cond_scale)
+        scheduled = weighted or (float(control_guidance_start), float(control_guidance_end)) != (0.0, 1.0)
+        if max_guidance_scale <= 1.0:            # as in denoise: the reference's non-CFG branch cannot run
+            c = self.unet.config
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied (1x{2 * 3 * c.addition_time_embed_dim} and "
+                               f"{c.projection_class_embeddings_input_dim}x{c.block_out_channels[0] * 4})")
+        self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        self._num_timesteps, self.scheduler._step_index = len(self.scheduler.timesteps), None
+        g = torch.linspace(min_guidance_scale, max_guidance_scale, Fw).unsqueeze(0).to(dev, out_dtype)    # window-local: a window is a clip
+        self._guidance_scale = _append_dims(g, latents.ndim)
+        guidance = g.to(torch.float32).contiguous()
+        added_time_ids = _get_add_time_ids(0.02, torch.float32, G, 6, 128, unet=self.unet).repeat(2 * G, 1).to(dev)
+        x = latents.to(torch.float32).contiguous().clone()
+        il = image_latents.to(dev, torch.float16).contiguous()
+        emb = image_embeddings.to(dev, torch.float16).repeat_interleave(G, 0).contiguous()               # halves-major: row half G + i
+        cond = controlnet_condition.to(dev, torch.float16)
+        cam = None if camera_cond is None else camera_cond.to(dev, torch.float16)
+        ptype, sig = PREDICTION_TYPES[self.scheduler.config.prediction_type], self.scheduler._sigmas_host
+        kinds = ["plain"] * len(plan) if not scheduled else [("weighted" if weighted else "plain") if on else "off" for on, _ in plan]
+        step_scales = [s for _, s in plan]
+        staging = W.WindowStaging(wplan, G)
+        # per group the slices a G-clip call on its windows would receive, [2G, Fw, ...] halves-major (and [G, Fw, h, w] pooled)
+        cut = lambda t, gi: torch.stack([t[:, s:s + Fw] for s in (wplan.starts[k] for k in staging.windows(gi))], 1).flatten(0, 1).contiguous()
+        sizes = tap_sizes(h, w, len(self.controlnet.config.block_out_channels))
+        inputs = []
+        for gi in range(groups):
+            level_base = None
+            if "weighted" in kinds:
+                cw = torch.ones((1, Ft, h, w), dtype=torch.float32, device=dev) if control_weight is None else control_weight.to(dev)
+                level_base = pool_control_weight(cut(cw, gi), sizes)
+            inputs.append((cut(cond, gi), None if cam is None else cut(cam, gi), level_base))
+        independent = G if G > 1 else 0                                     # one window per evaluation: one-clip launches
+        run = lambda st, sample, t_: self._networks_step(st.kind, sample, t_, st.emb, st.cond, st.cam, st.ids, controlnet_cond_scale,
+                                                         st.wbuf, overlap_streams, None, independent)
+        geometry = GraphKey(Bc=G, F=Fw, hw=(h, w), cond_shape=tuple(inputs[0][0].shape), cam_shape=None if cam is None else tuple(inputs[0][1].shape),
+                            kind=None, scale=None, unet=id(self.unet), controlnet=id(self.controlnet), unet_gen=self.unet._generation,
+                            controlnet_gen=self.controlnet._generation, overlap=bool(overlap_streams), networks_name=None,
+                            dispatch=ops.dispatch_key() + (("independent_clips", bool(independent)),)) if use_graph else None
+        weights = torch.from_numpy(wplan.weights).to(dev)
+        pred_all = torch.empty((2 * K, Fw, h, w, 4), dtype=torch.float32, device=dev) if groups > 1 else None
+        merged = torch.empty((1, Ft, 4, h, w), dtype=torch.float32, device=dev)
+        multistep = getattr(self.scheduler, "order", 1) == 2
+        d_prev = torch.empty_like(x) if multistep else None
+        live, loaded = {}, {}
+        try:
+            for i in range(self._num_timesteps):
+                t = self.scheduler._timesteps_host[i]
+                if self.scheduler._step_index is None:
+                    self.scheduler._init_step_index(t)
+                k = self.scheduler._step_index
+                kind = kinds[i]
+                st = live.get(kind)
+                if st is None:                   # the first step of its kind in this call
+                    key = geometry and geometry._replace(kind=kind, scale=float(controlnet_cond_scale) if kind == "plain" else None)
+                    st = live[kind] = (key and self._step_graphs.get(key)) or StepState(kind, run, key)
+                    st.windows = staging
+                    st.load(emb, added_time_ids, *inputs[0], self.controlnet)
+                    loaded[kind] = 0
+                    if use_graph and st.graph is None:
+                        staging.select(0)
+                        st.capture(self._step_graphs.pool_for(key), x, il, sig[k], t)
+                        self._step_graphs.insert(key, st)
+                for gi in range(groups):
+                    if loaded[kind] != gi:       # several groups share one state (and graph): this group's condition into it
+                        st.load(emb, added_time_ids, *inputs[gi], self.controlnet)
+                        loaded[kind] = gi
+                    st.fold(step_scales[i])
+                    staging.select(gi)
+                    pred_cl = st.step(x, il, sig[k], t)                                    # [2G, Fw, h, w, 4] fp32
+                    if groups > 1:               # halves-major rows of the K-window buffer
+                        pred_all[gi * G:(gi + 1) * G].copy_(pred_cl[:G])
+                        pred_all[K + gi * G:K + (gi + 1) * G].copy_(pred_cl[G:])
+                W.cfg_window_merge(pred_all if groups > 1 else pred_cl, guidance, weights, wplan.starts, Ft, out=merged)
+                if multistep:
+                    x = ops.multistep_step(merged, x, self.scheduler.coefficients(k, first=i == 0), d_prev)
+                else:
+                    x = ops.euler_step(merged, x, sig[k], sig[k + 1], ptype)
+                self.scheduler._step_index += 1
+                self.scheduler.is_scale_input_called = True
+                if callback_on_step_end is not None:
+                    cb_latents = x.to(out_dtype)
+                    outs = callback_on_step_end(self, i, t, {"latents": cb_latents})
+                    new = outs.pop("latents", cb_latents)
+                    if new is not x:
+                        x = new.to(torch.float32).contiguous().clone()
+        finally:                                 # a cached state serves the next call, windowed or not
+            for st in live.values():
+                st.windows = None
+        return x.to(out_dtype)
+
     @torch.no_grad()
     def __call__(self, image=None, controlnet_condition: torch.FloatTensor = None, height: int = 576, width: int = 1024,
                  num_frames: Optional[int] = None, num_inference_steps: int = 25, min_guidance_scale: float = 1.0,
@@ -490,7 +623,8 @@ class StableVideoDiffusionPipelineControlNet:
                  image_embeddings: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
                  use_graph: bool = True, overlap_streams: bool = True, control_guidance_start: float = 0.0,
                  control_guidance_end: float = 1.0, control_weight: Optional[torch.Tensor] = None,
-                 independent_clips: bool = False):
+                 independent_clips: bool = False, window_frames: Optional[int] = None, window_stride: Optional[int] = None,
+                 window_batch: Optional[int] = None):
         """Same signature as the reference (``pipeline...:316-340``; ``camera_cond`` from the ``_cam`` twin) plus
         ``image_embeddings`` ``[2,1,D]`` / ``image_latents`` ``[2,4,h,w]`` (the outputs of the CLIP / VAE-encode stages,
         ``:441,457``, for callers that have them already) and ``use_graph`` / ``overlap_streams`` (the loop as a replayed
@@ -511,9 +645,26 @@ class StableVideoDiffusionPipelineControlNet:
         when given; ``control_weight`` keeps its ``[K, F, h, w]`` form.  ``batch_size`` is taken from the list, ``num_videos_per_prompt``
         must be 1.  ``.frames`` is a list of K clips, clip k what a call with request k alone returns (``output_type="latent"``: K tensors
         ``[1, F, 4, h, w]``); every clip is decoded on its own.  A mismatched length is a ``ValueError`` naming the argument, raised
-        before any stage runs.  Guidance range, control scale and window are shared by the K clips."""
+        before any stage runs.  Guidance range, control scale and window are shared by the K clips.
+
+        ``window_frames`` / ``window_stride`` / ``window_batch`` (see ``denoise``; beyond the reference, default off): a long video of
+        ``num_frames`` frames from a model trained on ``window_frames``, denoised as overlapping windows whose predictions are blended at
+        every step.  One request per call (``batch_size * num_videos_per_prompt == 1``, not with ``independent_clips``);
+        ``controlnet_condition`` holds ``num_frames`` maps, ``camera_cond`` is ``[num_frames, 12]``, ``control_weight``
+        ``[num_frames, h, w]``; ``decode_chunk_size`` defaults to ``window_frames``.  Every window is conditioned on the same first image."""
         num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
         control_plan(num_inference_steps, controlnet_cond_scale, control_guidance_start, control_guidance_end)
+        if window_frames is not None:
+            from .windows import resolve
+            if independent_clips:
+                raise ValueError("`window_frames` serves one request: it does not go with `independent_clips`")
+            if batch_size * (num_videos_per_prompt or 1) != 1:
+                raise ValueError(f"`window_frames` serves one request: `batch_size` * `num_videos_per_prompt` must be 1; got "
+                                 f"{batch_size} * {num_videos_per_prompt}")
+            resolve(num_frames, window_frames, window_stride, window_batch)
+            decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else int(window_frames)
+        elif window_stride is not None or window_batch is not None:
+            raise ValueError("`window_stride` / `window_batch` need `window_frames` (the windowed loop is off without it)")
         if independent_clips:
             batch_size = self._check_independent_requests(image, controlnet_condition, generator, camera_cond, latents, image_embeddings,
                                                           image_latents, num_videos_per_prompt, num_frames)
@@ -575,7 +726,8 @@ class StableVideoDiffusionPipelineControlNet:
                                max_guidance_scale, controlnet_cond_scale, cam, callback_on_step_end,
                                callback_on_step_end_tensor_inputs, use_graph=use_graph, overlap_streams=overlap_streams,
                                control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                               control_weight=control_weight, independent_clips=independent_clips)
+                               control_weight=control_weight, independent_clips=independent_clips,
+                               **({} if window_frames is None else dict(window_frames=window_frames, window_stride=window_stride, window_batch=window_batch)))
         if not output_type == "latent":                                                     # :585-592
             if needs_upcasting:
                 self.vae.to(dtype=torch.float16)

@@ -28,7 +28,8 @@ class StableVideoDiffusionPipelineControlNet(_Base):
         """``**kw``: the base pipeline's further keyword arguments - ``image_embeddings``, ``image_latents``, ``use_graph``,
         ``overlap_streams`` and the control-strength arguments ``control_guidance_start``, ``control_guidance_end`` and
         ``control_weight`` (``controlnet_cond_scale`` may be one float per step), all as documented there - and ``independent_clips``:
-        K requests in one call, each its own clip, with ``camera_cond`` ``[K, F, 12]``."""
+        K requests in one call, each its own clip, with ``camera_cond`` ``[K, F, 12]``; and ``window_frames`` / ``window_stride`` /
+        ``window_batch``: a long video as overlapping windows, with ``camera_cond`` ``[num_frames, 12]`` sliced per window."""
         cam = torch.tensor(camera_cond, dtype=torch.float32)        # ..._cam.py:505: raises for None exactly like the reference
         return _Base.__call__(self, image, controlnet_condition, height, width, num_frames, num_inference_steps, min_guidance_scale,
                               max_guidance_scale, fps, motion_bucket_id, noise_aug_strength, decode_chunk_size, num_videos_per_prompt,

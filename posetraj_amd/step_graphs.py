@@ -50,13 +50,18 @@ def _into(buf, src):
 class StepState:
     """One kind of step.  ``run(state, sample, t)`` launches its networks.  With a ``key`` the state is static: it owns copies of the
     clip's inputs and its condition embedding at addresses a captured graph reads, ``capture`` makes the graph and ``step`` replays
-    it.  Without one it refers to the caller's tensors and ``step`` launches eagerly (the ControlNet's own cache holds the embedding)."""
+    it.  Without one it refers to the caller's tensors and ``step`` launches eagerly (the ControlNet's own cache holds the embedding).
+
+    ``windows`` (optional, ``posetraj_amd.windows.WindowStaging``; set per call by the windowed loop and cleared by it): the latents are a
+    long video ``[1, Ft, 4, h, w]`` and a step evaluates one group of its windows - the plan gives the size of ``xin`` and the staging
+    call, everything else is the state of a batch of that many clips (same key, same graph)."""
 
     emb = ids = cond = cam = cond_embed = xin = t = graph = pred = None
     wbase = wbuf = folded = None             # weighted: the pooled weights and the same times ``folded``, per tap size
+    windows = None
 
-    def __init__(self, kind, run, key=None):
-        self.kind, self.run, self.key = kind, run, key
+    def __init__(self, kind, run, key=None, windows=None):
+        self.kind, self.run, self.key, self.windows = kind, run, key, windows
 
     def load(self, emb, ids, cond, cam, level_base, controlnet):
         """The clip's inputs, in place when the state is static; "off" reads neither the control maps nor the camera."""
@@ -80,13 +85,17 @@ class StepState:
             self.folded = scale
 
     def _stage(self, x, il, sigma, t):
-        ops.scale_concat_input(x, il, sigma, out=self.xin)
+        if self.windows is None:
+            ops.scale_concat_input(x, il, sigma, out=self.xin)
+        else:
+            self.windows.stage(x, il, sigma, out=self.xin)
         self.t.fill_(float(t))
 
     def capture(self, pool, x, il, sigma, t):
         """Warm-up on a fresh stream (weight-only caches, allocator sizing), then the capture into ``pool``; both read defined values."""
         dev = x.device
-        self.xin = torch.empty((2 * x.shape[0], x.shape[1], x.shape[3], x.shape[4], 8), dtype=torch.float16, device=dev)
+        shape = (2 * x.shape[0], x.shape[1], x.shape[3], x.shape[4], 8) if self.windows is None else self.windows.input_shape(x.shape[3], x.shape[4])
+        self.xin = torch.empty(shape, dtype=torch.float16, device=dev)
         self.t = torch.zeros(1, dtype=torch.float32, device=dev)
         for sz, b in (self.wbase or {}).items():
             self.wbuf[sz].copy_(b)
@@ -104,7 +113,8 @@ class StepState:
     def step(self, x, il, sigma, t):
         """Latents ``x`` [Bc, F, 4, h, w] at ``sigma`` -> the fp32 channels-last prediction [2Bc, F, h, w, 4]."""
         if self.graph is None:
-            return self.run(self, ops.scale_concat_input(x, il, sigma).permute(0, 1, 4, 2, 3), t)     # [2Bc, F, 8, h, w] view
+            xin = ops.scale_concat_input(x, il, sigma) if self.windows is None else self.windows.stage(x, il, sigma)
+            return self.run(self, xin.permute(0, 1, 4, 2, 3), t)                                      # [2Bc, F, 8, h, w] view
         self._stage(x, il, sigma, t)
         self.graph.replay()
         return self.pred
